@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fwd+bwd frames/s of the AD-GS hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3]
+    python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR] [--full]
 
 One "frame" = per-frame deformation (when the config has dynamic objects) + GaussianRasterizer forward + backward with
 non-zero upstream gradients on colour, depth, accumulated opacity, flow and semantic; loss and optimizer are
@@ -17,9 +17,20 @@ Workloads (BASELINE.json configs):
     `--densify-every` iterations inside the timed loop (reported separately as densify_ms).  `value` = cameras rendered per
     second ("scaling": "strong": the iteration's work is fixed as N grows).  On one GPU the same code accumulates the cameras.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with "roofline" for the dominant kernel (algorithmic bytes per
-launch / HIP-event time of that kernel), "cpu_baseline" (the CPU oracle timed on the host cores), per-step HIP-event statistics
-(median / p10 / p90), the GPU-idle share of a step, per-step exchange times for N > 1, and secondary single-GPU measurements.
+Prints ONE JSON line on rank 0 with the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall time of
+one timed step), per-step HIP-event statistics (median / p10 / p90) and per-step exchange / densify times.  A plain run does only what
+that line needs: set-up, warm-up, exactly K timed steps, the line.  `--full` adds everything else the benchmark measures: the
+per-stage breakdown and the GPU-idle share of a step (HIP events around every stage in the warm-up, around the dominant kernel in the
+timed steps), "roofline" for the dominant kernel (algorithmic bytes per launch / HIP-event time of that kernel, HBM counters measured in
+child runs), "cpu_baseline" (the CPU oracle timed on the host cores) with parity against it, the multi-GPU self-checks and the
+secondary single-GPU measurements.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step handed its caller -- eager steps: the rendered images and radii
+of every camera of the step, the screen-space gradient and every parameter gradient; `--graph on`: the parameter gradients, all a
+graph replay returns -- as DIR/<name>.npy (float32; a fixed, seeded sample of the elements of an array too large for the 64 MB
+budget).  Inputs are seeded and the timed region always starts at entry 0 of the camera pool (step k renders entry k mod the pool
+size, however many settle windows ran); with densify/prune in the loop a dumping run settles for a fixed number of steps.  So two
+builds run with the same arguments can be compared output for output; the line names the dumped cameras (`config.dumped_outputs`).
 """
 import argparse
 import gc
@@ -698,6 +709,36 @@ def step_stats(ms):
             "steps_per_s_at_median_step": round(1e3 / med, 1) if med > 0 else None}
 
 
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: all files together stay below 64 MB (.npy headers included)
+DUMP_MAX_ARRAY_BYTES = 4 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write [(name, tensor)] as out_dir/<name>.npy, float32 (float64 stays float64, integers become float32).  An
+    array above its share of DUMP_BUDGET_BYTES is reduced to a fixed sample of its flattened elements: sorted unique indices drawn
+    with a seed that depends on the name and the size only, so every run with the same arguments writes the same elements."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = [(n, t) for n, t in arrays if t is not None]
+    share = min(DUMP_MAX_ARRAY_BYTES, DUMP_BUDGET_BYTES // max(len(arrays), 1))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        dtype = torch.float64 if flat.dtype == torch.float64 else torch.float32
+        cap = share // (8 if dtype == torch.float64 else 4)
+        n = int(flat.numel())
+        if n > cap:
+            rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, n)).encode()))
+            idx = np.unique(rng.integers(0, n, size=cap, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(dtype).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(t.shape), "stored": int(a.size), "sampled": n > cap}
+    return written
+
+
 def quick_measure(config, steps, device, use_fs, variant="default", mode=None, with_stats=False, warm=15, cameras=1, graph=False, env=None):
     """frames/s of another workload in the same process (single GPU): secondary information next to the headline, never `value`.
     cameras: size of the camera pool cycled per step; graph: forward + backward replayed as one HIP graph per camera
@@ -846,7 +887,12 @@ def main():
                     help="on: every camera's forward + backward is replayed as one HIP graph (adgs.graph; single GPU, not the iteration configs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-flow-sem", action="store_true", help="render without the flow / semantic outputs")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary single-GPU measurements (other configs, scene sensitivity)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary single-GPU measurements (other configs, scene sensitivity)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: stage breakdown, roofline and HBM counters, CPU baseline and parity, multi-GPU "
+                         "self-checks, secondary measurements (off: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (images, radii, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # the hosts only support dmabuf IPC: RCCL across processes needs this (set before HIP initialises)
@@ -977,15 +1023,30 @@ def main():
         raise SystemExit("--graph on: single GPU, one camera per step (the exchange of the multi-GPU step is issued eagerly)")
     cache = graphed_steps(my_pool, up_list) if use_graph else None
 
+    def param_names():
+        """Names of params(), in its order (the gradients a graph replay returns come in the same order)."""
+        if dynamic:
+            from adgs.model import _RAW
+            return [n.lstrip("_") for n in _RAW if getattr(model, n, None) is not None and getattr(model, n).numel() > 0]
+        return list(frame.leaf.keys())
+
+    # --dump-outputs: step `dump_at[0]` (the last timed one) keeps references to what it hands its caller; nothing is copied in the step
+    dump_at, captured = [-1], {"cams": [], "grads": []}
+
     def step(it=0, eager=False):
+        keep = it == dump_at[0]
         if cache is not None and not eager:
-            cache(it % pool_k)
+            grads = cache(it % pool_k)
+            if keep:
+                captured["grads"] = list(zip(param_names(), grads))
             return
         if factored:
             ex.begin(n_cams)                     # the all-gather starts from inside the backward, as soon as the last factor exists
         def one_camera(f):
             outs = f.forward(sink_for=ex.sink_for if factored else None)
             torch.autograd.backward(outs, up_list)
+            if keep:
+                captured["cams"].append((outs, f.last_radii, f.last_means2D.grad if isinstance(f, DeformFrame) else f.means2D.grad))
             if densify_every:
                 with torch.no_grad():
                     model.add_densification_stats(dict(viewspace_points=f.last_means2D, radii=f.last_radii))
@@ -1015,6 +1076,8 @@ def main():
             dp.allreduce_gradients(params(), force=force_coll)
             e1.record()
             ex_events.append((e0, e1))
+        if keep:                                 # the exchanged gradients, before a densify step replaces the parameters
+            captured["grads"] = list(zip(param_names(), [p.grad for p in params()]))
         if densify_every and (it + 1) % densify_every == 0:
             with torch.no_grad():
                 e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
@@ -1055,9 +1118,10 @@ def main():
     # Order of the W warm-up steps: the profiled ones FIRST, then every piece of host-side set-up of the timed region (event pools,
     # reading the stage events back, a garbage collection), then the remaining plain warm-up steps, then the timed region at once:
     # a GPU left idle for the milliseconds that set-up takes runs its next step up to 1 ms slower (clocks), which is 3.5 % of a
-    # 20-step run when it lands inside it.
+    # 20-step run when it lands inside it.  A plain run (no --full) reports no stage times: it brackets nothing, neither in the warm-up
+    # nor in the timed region.
     stages_all, dom, gpu_idle, stage_step_ms = None, None, None, None
-    n_prof = min(4, args.warmup // 2)
+    n_prof = min(4, args.warmup // 2) if args.full else 0
     if os.environ.get("ADGS_BENCH_SETTLE", "1") != "0":
         run(max(8, 2 * pool_k))                       # set-up: every camera of the pool rendered (capacity hints, allocator, the cameras' tile-order hints) before anything is measured
         sync()
@@ -1081,8 +1145,10 @@ def main():
                     "gpu_not_in_adgs_kernels_ms": round(prof_step_ms - sum(per_step.values()), 4),
                     "note": "from %d warm-up steps with every stage bracketed by HIP events (each bracket adds a bubble: an upper bound)" % n_prof}
         dom = max(stages_all, key=lambda k: stages_all[k][0] * max(stages_all[k][1], 1))
-    prof = _lib.StageProfiler()
-    prof.reserve(2 * args.steps * max(len(frames), 1) * (1 if dom else 11) + 64)      # no event creation inside the timed region
+    prof = None
+    if args.full:
+        prof = _lib.StageProfiler()
+        prof.reserve(2 * args.steps * max(len(frames), 1) * (1 if dom else 11) + 64)      # no event creation inside the timed region
     gc.collect()
     # Settle phase (setup, not a measurement), AFTER every piece of host-side set-up and right in front of the warm-up steps: the GPU must come
     # into the timed region busy.  (Until round 5 the settle windows ran first and the stage-profile read-back + garbage collection came after
@@ -1090,6 +1156,9 @@ def main():
     # than steady state -- 1.075 against 1.03 ms medians -- while the clocks came back.)  A fresh process on a fresh box shows one-off stalls of 0.1-0.6 s in its first
     # second (driver / allocator / clock ramp).  Windows of 20 untimed steps run until two consecutive windows agree within 10 %
     # (at most 8 windows), then the contract's W warm-up steps and K timed steps follow unchanged.
+    # --dump-outputs with densify/prune in the loop: the model at the dumped step depends on how many densify calls ran before it, so
+    # the settle phase then always runs all of its windows (a fixed number of steps before the timed region)
+    fixed_settle = bool(args.dump_outputs and densify_every)
     settle_steps = 0
     if os.environ.get("ADGS_BENCH_SETTLE", "1") != "0":
         prev_w, agree = None, 0
@@ -1106,21 +1175,47 @@ def main():
                 w = float(tw.item())
             agree = agree + 1 if (prev_w is not None and abs(w - prev_w) <= 0.1 * min(w, prev_w)) else 0
             prev_w = w
-            if agree >= 2:
+            if agree >= 2 and not fixed_settle:
                 break
+    # the timed region starts at pool entry 0 whatever the number of settle windows: step k of it renders entry k mod pool_k, in every run
+    align = -(it_counter[0] + args.warmup - n_prof) % pool_k
+    run(align)
+    settle_steps += align
     run(args.warmup - n_prof)
-    prof.enable(True, stages=[dom] if dom else None)       # --warmup 0: no breakdown yet, time every stage (a mask store: no gap)
+    if prof is not None:
+        prof.enable(True, stages=[dom] if dom else None)       # --warmup 0: no breakdown yet, time every stage (a mask store: no gap)
     if ex is not None:
         ex.timing = []
     del ex_events[:]; del densify_events[:]
     reruns0 = _lib.frame_status()["eager_reruns"]
+    dump_at[0] = it_counter[0] + args.steps - 1
     elapsed, step_ms = timed_loop(lambda i: run(1), args.steps, sync, barrier)
-    prof.enable(False)
-    stages = prof.collect()
+    dump_at[0] = -1
+    stages = None
+    if prof is not None:
+        prof.enable(False)
+        stages = prof.collect()
     capacity_reruns = _lib.frame_status()["eager_reruns"] - reruns0
     graph_ok = cache.validate(repair=False) if cache is not None else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = []
+        for k, (outs, radii, g2d) in enumerate(captured["cams"]):
+            pre = "" if len(captured["cams"]) == 1 else "cam%d_" % k
+            arrays += list(zip([pre + n for n in ("color", "depth", "opacity", "flow", "semantic")], outs))
+            arrays += [(pre + "radii", radii), (pre + "grad_means2D", g2d)]
+        arrays += [("grad_" + n, g) for n, g in captured["grads"]]
+        last = it_counter[0] - 1
+        if iteration_mode:
+            cams_dumped = [{"camera": i, "t": round(cam_times[i], 6)} for i in my]
+        else:
+            k = last % pool_k
+            cams_dumped = [{"pool_entry": k, "camera": rank + world * k, "t": round(pools[rank][k][1], 6)}]
+        dumped = {"dir": args.dump_outputs, "timed_step": args.steps - 1, "cameras": cams_dumped,
+                  "P_after_step": int(model.get_pts_num) if dynamic else P, "arrays": dump_outputs(args.dump_outputs, arrays)}
+    captured["cams"], captured["grads"] = [], []
     multi_gpu = None
-    if world > 1 or force_coll:
+    if (world > 1 or force_coll) and args.full:
         # Self-verifying multi-GPU figures (for the day a multi-GPU node runs this): the rank count RCCL itself reports (an
         # all-reduce of ones), every rank's own time per step and pair counts (cameras differ: load imbalance), and the exchange
         # timed with BOTH forms of the dense reduction in this one run (a short untimed loop with the other form).
@@ -1214,8 +1309,10 @@ def main():
             dms = [a.elapsed_time(b) for a, b in densify_events]
             config["densify_ms"] = {"mean": round(sum(dms) / len(dms), 4), "calls": len(dms), "P_end": int(model.get_pts_num),
                                     "ms_per_step_excl_densify": round((elapsed * 1e3 - sum(dms)) / args.steps, 4)}
+        if dumped is not None:
+            config["dumped_outputs"] = dumped
         roof = None
-        if frame is not None:
+        if frame is not None and args.full:
             outs = frame.forward()
             stats = _lib.frame_stats()
             V = int((frame.last_radii > 0).sum().item())
@@ -1323,7 +1420,7 @@ def main():
                     result["stage_rooflines"][k] = r
         else:
             result["config"] = config
-        secondary = world == 1 and not force_coll and not args.no_secondary and args.config == "C3" and not iteration_mode
+        secondary = args.full and world == 1 and not force_coll and not args.no_secondary and args.config == "C3" and not iteration_mode
         if secondary:
             # the other single-GPU configs of BASELINE.json, same build, same process (secondary: `value` stays the C3 headline), the
             # mandatory C1 CPU baseline (OpenMP and single thread), and the scene-sensitivity lines: two C3-sized scenes that do NOT
@@ -1412,7 +1509,7 @@ def main():
                 result["scene_sensitivity"] = sens
             except Exception as exc:                     # secondary information must never cost the headline line
                 result["other_configs"] = "failed: %r" % (exc,)
-        if world == 1 and not args.no_cpu_baseline and frame is not None and not iteration_mode:
+        if args.full and world == 1 and not args.no_cpu_baseline and frame is not None and not iteration_mode:
             if isinstance(frame, DeformFrame):
                 pkg, flow = frame.activated()
                 sc_cpu = dict(sc, means3D=pkg["xyz"], opacities=pkg["opacity"], scales=pkg["scales"], rotations=pkg["rotation"],

@@ -22,7 +22,7 @@ def _free_port():
 def test_ranks_finish_and_print_one_json_line(config, exchange, world):
     env = dict(os.environ, ADGS_BENCH_BACKEND="gloo", ADGS_DP_EXCHANGE=exchange, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port",
-           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--config", config]
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--config", config, "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -97,3 +97,52 @@ def test_multi_rank_training_loop_keeps_replicas_identical_and_matches_one_proce
     assert all(abs(x - y) <= 2e-4 * abs(y) + 1e-7 for x, y in zip(a, b)), (a, b)
     size = lambda out: [l for l in out.splitlines() if "Gaussians at the end" in l][0].split(";")[1]
     assert size(two.stdout) == size(one.stdout)                       # the same rows were cloned / split / pruned
+
+
+def _plain_run(config, steps, out_dir, extra=()):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "3", "--config", config,
+           "--dump-outputs", str(out_dir)] + list(extra)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["ADGS_BENCH_DUMP_STEPS"] = "1000"                  # the per-step HIP-event series of the timed region, every step
+    out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("config,extra", [("T3", []), ("C1", ["--graph", "on"])])
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_step(config, extra, tmp_path):
+    """A plain run (no --full): exactly --steps timed steps (one HIP-event interval each), the headline fields and nothing measured
+    beside them, and with --dump-outputs what the last timed step returned, as float32 .npy files inside the 64 MB budget.  The timed
+    region starts at pool entry 0 whatever the settle phase did: the last of 5 steps renders entry 4 of the 16-camera pool, the last
+    of 21 steps entry 4 again (the same radii), the last of 6 steps entry 5 (other radii)."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    d = _plain_run(config, 5, out_dir, extra)
+    assert d["metric"] == "fwd+bwd frames/s" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 5 and d["warmup"] == 3 and d["value"] > 0 and abs(d["value"] - 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-3
+    assert len(d["config"]["step_ms_series"]) == 5
+    assert not {"roofline", "stages_ms", "cpu_baseline", "parity", "other_configs"} & set(d)
+    dump = d["config"]["dumped_outputs"]
+    assert dump["timed_step"] == 4 and [c["pool_entry"] for c in dump["cameras"]] == [4] and dump["cameras"][0]["camera"] == 4
+    names = set(dump["arrays"])
+    files = sorted(os.listdir(out_dir))
+    assert files == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    grads = [n for n in names if n.startswith("grad_") and n != "grad_means2D"]
+    assert grads and all(np.load(out_dir / (n + ".npy")).dtype == np.float32 for n in names)
+    assert all(np.isfinite(np.load(out_dir / (n + ".npy"))).all() for n in names)
+    assert any(np.abs(np.load(out_dir / (n + ".npy"))).max() > 0 for n in grads)
+    if extra:                                         # a graph replay returns the parameter gradients only
+        assert names == set(grads)
+        return
+    assert {"color", "depth", "opacity", "flow", "semantic", "radii", "grad_means2D"} <= names
+    assert np.load(out_dir / "color.npy").size == 3 * 208 * 320
+    radii = np.load(out_dir / "radii.npy")
+    same = _plain_run(config, 21, tmp_path / "same")
+    assert len(same["config"]["step_ms_series"]) == 21 and same["config"]["dumped_outputs"]["cameras"][0]["pool_entry"] == 4
+    assert np.array_equal(np.load(tmp_path / "same" / "radii.npy"), radii)
+    other = _plain_run(config, 6, tmp_path / "other")
+    assert len(other["config"]["step_ms_series"]) == 6 and other["config"]["dumped_outputs"]["cameras"][0]["pool_entry"] == 5
+    assert not np.array_equal(np.load(tmp_path / "other" / "radii.npy"), radii)

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; o=$R/gpurun_out/ab_env_$1; mkdir -p $o; cd $R
 run() { # name, env...
   name=$1; shift
-  env "$@" timeout 300 python bench.py --steps ${STEPS:-200} --warmup ${WARM:-30} --no-secondary --no-cpu-baseline $EXTRA > $o/$name.json 2> $o/$name.err
+  env "$@" timeout 300 python bench.py --steps ${STEPS:-200} --warmup ${WARM:-30} --no-secondary --no-cpu-baseline --full $EXTRA > $o/$name.json 2> $o/$name.err
   python - <<PY
 import json
 try:

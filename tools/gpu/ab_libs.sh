@@ -7,7 +7,7 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   lib=$L/libadgs_hip_$v.so; [ $v = default ] && lib=$L/libadgs_hip.so
-  ADGS_LIB=$lib ADGS_BENCH_PMC=0 python bench.py --steps ${STEPS:-100} --warmup 10 --no-secondary --no-cpu-baseline ${CFG:+--config $CFG} > $o/bench_${v}_$i.json 2> $o/bench_${v}_$i.err
+  ADGS_LIB=$lib ADGS_BENCH_PMC=0 python bench.py --steps ${STEPS:-100} --warmup 10 --full --no-secondary --no-cpu-baseline ${CFG:+--config $CFG} > $o/bench_${v}_$i.json 2> $o/bench_${v}_$i.err
   python - <<PY
 import json
 try:

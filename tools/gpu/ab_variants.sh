@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; o=$R/gpurun_out/ab; mkdir -p $o; cd $R
 L=$R/ad-gs_amd/lib
 for v in "$@"; do
   lib=$L/libadgs_hip_$v.so; [ $v = default ] && lib=$L/libadgs_hip.so
-  ADGS_LIB=$lib python bench.py --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --cameras 1 > $o/bench_$v.json 2> $o/bench_$v.err
+  ADGS_LIB=$lib python bench.py --steps 100 --warmup 10 --full --no-secondary --no-cpu-baseline --cameras 1 > $o/bench_$v.json 2> $o/bench_$v.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 o=$R/gpurun_out/${1:-r06_prof}; mkdir -p $o
 cd /tmp && export TMPDIR=/tmp
 export ADGS_BENCH_PMC=0
-B="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+B="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -o stats -- $B > $o/stats.log 2>&1
 export ADGS_BENCH_SKIP_STATS=1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $o/fetch -o fetch -- $B > $o/fetch.log 2>&1

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; tag=${1:-r05}; shift; o=$R/gpurun_out/$tag; mkdir -p $o; cd 
 timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider -rf "$@" > $o/gpu_tests.log 2>&1
 grep -E "^(FAILED|ERROR)|passed|failed" $o/gpu_tests.log | cut -c1-400 | tail -60
 if [ -z "$NOBENCH" ]; then
-timeout 900 python bench.py --steps 20 --warmup 5 > $o/bench_driver.json 2> $o/bench_driver.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $o/bench_driver.json 2> $o/bench_driver.err
 python - <<PY
 import json
 try:
