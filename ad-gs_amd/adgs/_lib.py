@@ -43,6 +43,19 @@ SIGNATURES = {
     "adgs_raster_backward_rawsh": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p,
                                          c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
+    # the four forward entries with a trailing const adgs_raster_options* (NULL = the defaults)
+    "adgs_raster_forward_opts": (c_i, [ALLOC_FN, c_p, ALLOC_FN, c_p, ALLOC_FN, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i,
+                                       c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i,
+                                       c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "adgs_raster_render_opts": (c_i, [ALLOC_FN, c_p, ALLOC_FN, c_p, ALLOC_FN, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i,
+                                      c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i,
+                                      c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "adgs_raster_forward_rawsh_opts": (c_i, [ALLOC_FN, c_p, ALLOC_FN, c_p, ALLOC_FN, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i,
+                                             c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_f, c_f,
+                                             c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "adgs_raster_render_rawsh_opts": (c_i, [ALLOC_FN, c_p, ALLOC_FN, c_p, ALLOC_FN, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i,
+                                            c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_f, c_f,
+                                            c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
     "adgs_mark_visible": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_knn_workspace_bytes": (ctypes.c_size_t, [c_i]),
     "adgs_knn_dist2": (c_i, [c_i, c_p, c_p, c_p, c_p]),
@@ -114,6 +127,19 @@ SIGNATURES = {
     "adgs_test_sort_pairs_u64": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
     "adgs_test_sort_pairs_u32": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
 }
+
+
+class RasterOptions(ctypes.Structure):
+    """adgs_raster_options (include/adgs_rasterizer.h); struct_bytes is filled in by raster_options()."""
+    _fields_ = [("struct_bytes", ctypes.c_uint64), ("antialiasing", ctypes.c_int32)]
+
+
+def raster_options(antialiasing=False):
+    """An adgs_raster_options for the `_opts` forward entries."""
+    o = RasterOptions()
+    o.struct_bytes = ctypes.sizeof(RasterOptions)
+    o.antialiasing = 1 if antialiasing else 0
+    return o
 
 
 class FrameStats(ctypes.Structure):

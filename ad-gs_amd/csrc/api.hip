@@ -364,17 +364,21 @@ static OrderHints* order_hints() {
 // (W, H, P).  A state that reaches the backward under another address (cloned / offloaded saved tensors) or another shape is "not
 // found": the backward then carves by today's environment and zeroes the accumulator lines itself -- it never trusts a stale entry.
 // tile_order / sh_staging / timeline: the backward's own measurement knobs (ADGS_TILE_ORDER, ADGS_NO_SH_STAGING, ADGS_TIMELINE_BWD), read by the FORWARD
-struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
-// FrameCfg <-> the configuration word in the image state's header (kernels.h: PreprocessArgs::cfg_word)
+// antialiasing: the forward ran the opacity-compensated 2D filter (adgs_raster_options) -- its backward differentiates through it, whatever it is asked
+struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; int antialiasing = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
+// FrameCfg <-> the configuration word in the image state's header (kernels.h: PreprocessArgs::cfg_word): magic 0xAD6 in bits 20..31, flags v2 /
+// tile_order / sh_staging / timeline / order_ready in bits 19..15, antialiasing in bit 14, ppl (1, 2 or 4) in bits 8..13, cell_tiles in bits 0..7.
+// (Until the filter existed ppl had bits 8..14; every word a library of that layout wrote reads the same here, bit 14 was always 0.)
 static uint32_t frame_cfg_word(const FrameCfg& c) {
 	return 0xAD600000u | ((uint32_t)(c.v2 & 1) << 19) | ((uint32_t)(c.tile_order & 1) << 18) | ((uint32_t)(c.sh_staging & 1) << 17) | ((uint32_t)(c.timeline & 1) << 16) |
-	       ((uint32_t)(c.order_ready & 1) << 15) |
-	       ((uint32_t)(c.ppl & 0x7f) << 8) | (uint32_t)(c.cell_tiles & 0xff);
+	       ((uint32_t)(c.order_ready & 1) << 15) | ((uint32_t)(c.antialiasing & 1) << 14) |
+	       ((uint32_t)(c.ppl & 0x3f) << 8) | (uint32_t)(c.cell_tiles & 0xff);
 }
 static bool frame_cfg_from_word(uint32_t w, FrameCfg* c) {
 	if ((w & 0xFFF00000u) != 0xAD600000u) return false;
-	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x7fu) };
+	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x3fu) };
 	c->tile_order = (int)((w >> 18) & 1u); c->sh_staging = (int)((w >> 17) & 1u); c->timeline = (int)((w >> 16) & 1u); c->order_ready = (int)((w >> 15) & 1u);
+	c->antialiasing = (int)((w >> 14) & 1u);
 	return c->cell_tiles >= 1 && (c->ppl == 1 || c->ppl == 2 || c->ppl == 4);
 }
 struct FrameKey {
@@ -516,7 +520,8 @@ extern "C" int adgs_device_check(void) {
 }
 
 // training = false: the forward-only render (adgs_raster_render*): nothing is kept for a backward
-static int raster_forward_impl(const ShSource* sh_src, bool training,
+// antialiasing: the opacity-compensated 2D filter (adgs_raster_options), recorded in the frame's configuration for its backward
+static int raster_forward_impl(const ShSource* sh_src, bool training, int antialiasing,
 	adgs_alloc_fn geometryBuffer, void* geometryUser,
 	adgs_alloc_fn binningBuffer, void* binningUser,
 	adgs_alloc_fn imageBuffer, void* imageUser,
@@ -586,6 +591,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training,
 		uint32_t frame_word = 0; bool order_tiles = false;
 		{
 			FrameCfg fcfg{ 1, cell_tiles, ppl };
+			fcfg.antialiasing = antialiasing ? 1 : 0;
 			fcfg.tile_order = env_int("ADGS_TILE_ORDER", 1) != 0; fcfg.sh_staging = env_str("ADGS_NO_SH_STAGING") == nullptr; fcfg.timeline = env_int("ADGS_TIMELINE_BWD", 0) != 0;
 			// fewer tiles than wave slots: nothing to balance, neither in the backward nor in the forward
 			order_tiles = wtiles >= 2048 && fcfg.tile_order;
@@ -638,6 +644,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training,
 		pa.bucket_count = nullptr;
 		pa.cfg_word = img.header; pa.cfg_value = frame_word;
 		pa.ddir = geom.ddir;      // raw-SH path: the backward will not read the `rest` rows a second time
+		pa.antialias = antialiasing ? 1 : 0;
 		// bucket binning accumulates the fine-tile total and a few device words, and splits its cells by a snapshot of slab bounds (the
 		// camera's own, else the thread's latest): zeroed / copied by the sh0 kernel on the raw-SH path (no launch of its own), by bin_prepare otherwise
 		FramePrologue pro{ nullptr, 0, nullptr, nullptr, 0 };
@@ -877,6 +884,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training,
 	uint32_t frame_word = 0;
 	{
 		FrameCfg fcfg{ 0, 1, 4 };
+		fcfg.antialiasing = antialiasing ? 1 : 0;
 		fcfg.sh_staging = env_str("ADGS_NO_SH_STAGING") == nullptr;
 		remember_frame(FrameKey{ ichunk, gchunk, width, height, P }, fcfg);
 		frame_word = frame_cfg_word(fcfg);
@@ -898,6 +906,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training,
 	memset(&pa.sh_src, 0, sizeof(pa.sh_src)); pa.sh0 = nullptr; pa.gacc = nullptr; pa.fine_total = nullptr;
 	pa.bucket_count = nullptr;
 	pa.cfg_word = img.header; pa.cfg_value = frame_word; pa.ddir = nullptr;
+	pa.antialias = antialiasing ? 1 : 0;
 	if (sh_src) { set_error("the raw-SH entry points need the default (v2) pipeline (not ADGS_RASTER_MODE=classic, D_S <= ADGS_V2_MAX_SEMANTIC)"); return -1; }
 	{ StageTimer t(ST_PREPROCESS, stream); if (launch_preprocess_fwd(pa, stream) != 0) return -1; }
 	ADGS_LAUNCH_CHECK(debug, stream);
@@ -1051,6 +1060,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		pa.out_flow = ra.do_flow ? dL_dflow : nullptr; pa.out_sem = ra.do_sem ? dL_dsemantic : nullptr; pa.D_S = D_S;
 		pa.sh_staging = cfg.sh_staging;
 		pa.ddir = geom.ddir;
+		pa.antialias = cfg.antialiasing;
 		{ StageTimer t(ST_PREPROCESS_BWD, stream); if (launch_preprocess_bwd(pa, stream) != 0) return -1; }
 		ADGS_LAUNCH_CHECK(debug, stream);
 		return 0;
@@ -1095,9 +1105,45 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 	pa.gacc = nullptr; pa.splats = nullptr; pa.W = width; pa.H = height; pa.out_mean2D = nullptr; pa.out_conic = nullptr; pa.out_opacity = nullptr; pa.out_color = nullptr; pa.out_depth = nullptr;
 	pa.out_flow = nullptr; pa.out_sem = nullptr; pa.D_S = D_S;
 	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr;
+	// anti-aliased frame: the blend's atomics left dL/d(effective opacity) in dL_dopacity; the preprocess backward rescales it in place and
+	// reads the effective opacity from the Splat lines
+	pa.antialias = cfg.antialiasing;
+	if (cfg.antialiasing) { pa.out_opacity = dL_dopacity; pa.splats = geom.splats; }
 	{ StageTimer t(ST_PREPROCESS_BWD, stream); if (launch_preprocess_bwd(pa, stream) != 0) return -1; }
 	ADGS_LAUNCH_CHECK(debug, stream);
 	return 0;
+}
+
+// adgs_raster_options (include/adgs_rasterizer.h): NULL = the defaults; min(struct_bytes, sizeof) bytes are read, members beyond the
+// caller's struct_bytes keep their defaults, a struct_bytes that does not reach the last member this library requires is refused
+static int read_raster_options(const adgs_raster_options* o, const char* who, int* antialiasing) {
+	*antialiasing = 0;
+	if (!o) return 0;
+	if (o->struct_bytes < offsetof(adgs_raster_options, antialiasing) + sizeof(int32_t) || o->struct_bytes > 4096) {
+		set_error(std::string(who) + ": adgs_raster_options.struct_bytes must be sizeof(adgs_raster_options) of the caller's header"); return -1;
+	}
+	adgs_raster_options full;
+	memset(&full, 0, sizeof(full));
+	memcpy(&full, o, std::min<size_t>((size_t)o->struct_bytes, sizeof(full)));
+	if (full.antialiasing != 0 && full.antialiasing != 1) { set_error(std::string(who) + ": adgs_raster_options.antialiasing must be 0 or 1"); return -1; }
+	*antialiasing = full.antialiasing;
+	return 0;
+}
+
+extern "C" int adgs_raster_forward_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options) {
+	int aa = 0;
+	if (read_raster_options(options, "adgs_raster_forward_opts", &aa) != 0) return -1;
+	return raster_forward_impl(nullptr, true, aa, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
+		width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic,
+		inv_depth, radii, debug, stream);
 }
 
 extern "C" int adgs_raster_forward(
@@ -1108,13 +1154,26 @@ extern "C" int adgs_raster_forward(
 	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
 	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
 	int inv_depth, int* radii, int debug, void* stream) {
-	return raster_forward_impl(nullptr, true, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
+	return adgs_raster_forward_opts(geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic, inv_depth, radii, debug, stream, nullptr);
+}
+
+// The forward-only render: adgs_raster_forward's arguments and images, nothing kept for a backward (include/adgs_rasterizer.h)
+extern "C" int adgs_raster_render_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options) {
+	int aa = 0;
+	if (read_raster_options(options, "adgs_raster_render_opts", &aa) != 0) return -1;
+	return raster_forward_impl(nullptr, false, aa, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
 		width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp,
 		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic,
 		inv_depth, radii, debug, stream);
 }
 
-// The forward-only render: adgs_raster_forward's arguments and images, nothing kept for a backward (include/adgs_rasterizer.h)
 extern "C" int adgs_raster_render(
 	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
 	int P, int D, int M, int D_S, const float* background, int width, int height,
@@ -1123,10 +1182,7 @@ extern "C" int adgs_raster_render(
 	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
 	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
 	int inv_depth, int* radii, int debug, void* stream) {
-	return raster_forward_impl(nullptr, false, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
-		width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic,
-		inv_depth, radii, debug, stream);
+	return adgs_raster_render_opts(geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic, inv_depth, radii, debug, stream, nullptr);
 }
 
 extern "C" int adgs_raster_backward(
@@ -1171,6 +1227,25 @@ static int check_sh_source(const adgs_sh_source* sh, int P, int M, const char* w
 	return 0;
 }
 
+extern "C" int adgs_raster_forward_rawsh_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options) {
+	int aa = 0;
+	if (read_raster_options(options, "adgs_raster_forward_rawsh_opts", &aa) != 0) return -1;
+	if (P > 0 && check_sh_source(sh, P, M, "adgs_raster_forward_rawsh") != 0) return -1;
+	if (P <= 0) return 0;
+	const ShSource src = to_sh_source(sh);
+	return raster_forward_impl(&src, true, aa, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
+		width, height, means3D, nullptr, nullptr, flow_points, semantic, opacities, scales, scale_modifier, rotations, nullptr,
+		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, img_opacity, img_flow, img_semantic,
+		inv_depth, radii, debug, stream);
+}
+
 extern "C" int adgs_raster_forward_rawsh(
 	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
 	int P, int D, int M, int D_S, const float* background, int width, int height,
@@ -1179,10 +1254,23 @@ extern "C" int adgs_raster_forward_rawsh(
 	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
 	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
 	int inv_depth, int* radii, int debug, void* stream) {
-	if (P > 0 && check_sh_source(sh, P, M, "adgs_raster_forward_rawsh") != 0) return -1;
+	return adgs_raster_forward_rawsh_opts(geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background, width, height, means3D, sh, flow_points, semantic, opacities, scales, scale_modifier, rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, img_opacity, img_flow, img_semantic, inv_depth, radii, debug, stream, nullptr);
+}
+
+extern "C" int adgs_raster_render_rawsh_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options) {
+	int aa = 0;
+	if (read_raster_options(options, "adgs_raster_render_rawsh_opts", &aa) != 0) return -1;
+	if (P > 0 && check_sh_source(sh, P, M, "adgs_raster_render_rawsh") != 0) return -1;
 	if (P <= 0) return 0;
 	const ShSource src = to_sh_source(sh);
-	return raster_forward_impl(&src, true, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
+	return raster_forward_impl(&src, false, aa, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
 		width, height, means3D, nullptr, nullptr, flow_points, semantic, opacities, scales, scale_modifier, rotations, nullptr,
 		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, img_opacity, img_flow, img_semantic,
 		inv_depth, radii, debug, stream);
@@ -1196,13 +1284,7 @@ extern "C" int adgs_raster_render_rawsh(
 	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
 	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
 	int inv_depth, int* radii, int debug, void* stream) {
-	if (P > 0 && check_sh_source(sh, P, M, "adgs_raster_render_rawsh") != 0) return -1;
-	if (P <= 0) return 0;
-	const ShSource src = to_sh_source(sh);
-	return raster_forward_impl(&src, false, geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background,
-		width, height, means3D, nullptr, nullptr, flow_points, semantic, opacities, scales, scale_modifier, rotations, nullptr,
-		viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, img_opacity, img_flow, img_semantic,
-		inv_depth, radii, debug, stream);
+	return adgs_raster_render_rawsh_opts(geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background, width, height, means3D, sh, flow_points, semantic, opacities, scales, scale_modifier, rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, img_opacity, img_flow, img_semantic, inv_depth, radii, debug, stream, nullptr);
 }
 
 extern "C" int adgs_raster_backward_rawsh(
@@ -1360,7 +1442,7 @@ extern "C" long long adgs_test_v2_scanned_candidates(const char* img_buffer, int
 	return sum_tile_words(v.img.tile_scanned, v.wtiles, (hipStream_t)stream_);
 }
 // sizeof of the structs that cross the ABI by pointer: lets a binding check its mirror (which: 0 adgs_sh_source, 1 adgs_sh_grads,
-// 2 adgs_frame_stats, 3 adgs_frame_status, 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam)
+// 2 adgs_frame_stats, 3 adgs_frame_status, 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam, 7 adgs_raster_options)
 extern "C" unsigned long long adgs_test_env_reads(void) { return g_env_reads.load(); }
 extern "C" size_t adgs_test_abi_sizeof(int which) {
 	switch (which) {
@@ -1371,6 +1453,7 @@ extern "C" size_t adgs_test_abi_sizeof(int which) {
 	case 4: return sizeof(adgs_func_eval);
 	case 5: return sizeof(adgs_adam_group);
 	case 6: return sizeof(adgs_sh_adam);
+	case 7: return sizeof(adgs_raster_options);
 	default: return 0;
 	}
 }

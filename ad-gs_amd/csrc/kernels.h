@@ -35,6 +35,9 @@ struct PreprocessArgs {
 	// raw-SH path, 16 coefficients: d(colour channel c)/d(view direction) of every visible Gaussian, [9][P] (dx / dy / dz of channels 0..2 in
 	// planes 0..8) -- 36 bytes that spare the preprocess BACKWARD its second pass over the 180-byte `rest` rows (nullptr: not wanted)
 	float* ddir;
+	// != 0: the opacity-compensated 2D filter (anti-aliased splatting): opacity * sqrt(max(det(cov2D) / det(cov2D + 0.3 I), 2.5e-5)) wherever the
+	// opacity is used after the projection; radii and rectangles come from the dilated covariance as before
+	int antialias;
 };
 
 int launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t stream);
@@ -91,6 +94,10 @@ struct PreprocessBwdArgs {
 	int D_S;
 	int sh_staging;                  // 0: ADGS_NO_SH_STAGING was set when the FORWARD of this frame ran (api.hip: FrameCfg)
 	const float* ddir;               // [9][P] written by this frame's preprocess forward (PreprocessArgs.ddir) or nullptr: read the `rest` rows again
+	// != 0: the forward of this frame ran the opacity-compensated 2D filter (PreprocessArgs::antialias).  The gradient of the effective opacity
+	// (v2: the accumulator line; classic: out_opacity, filled by the blend's atomics and rescaled IN PLACE here) is turned into that of the
+	// opacity, and its share through the filter factor joins the 2D covariance gradient.  Classic reads the effective opacity from `splats`.
+	int antialias;
 };
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream);
 

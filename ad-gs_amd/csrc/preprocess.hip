@@ -148,10 +148,12 @@ __device__ __forceinline__ PreIn load_pre_in(const PreprocessArgs& a, const int 
 	return in;
 }
 
-template <bool STAGED>
+// AA: the opacity-compensated 2D filter (PreprocessArgs::antialias) -- a template parameter, so that the instantiations without it are the
+// code they were before the option existed
+template <bool STAGED, bool AA>
 __device__ __forceinline__ PreOut preprocess_one(const PreprocessArgs& a, const int idx, const float* s_sh, uint32_t* s_cell, const PreIn& in);
 
-template <bool STAGED>
+template <bool STAGED, bool AA>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreprocessArgs a) {
 	extern __shared__ float s_sh[];
 	__shared__ uint32_t s_cell[MAX_CELLS];     // bucket binning: this workgroup's (cell, Gaussian) pair count per coarse cell
@@ -187,7 +189,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreprocessArgs a) {
 	if (STAGED || a.bucket_count) __syncthreads();
 	if (a.v2 && !a.bucket_count && idx < SCAN_AUX_SLOTS) a.fine_total[idx] = 0ull;     // counters of the scan's side sum (P >= 1 block: always covered)
 	PreOut o = { 0u, 0u };
-	if (idx < a.P) o = preprocess_one<STAGED>(a, idx, s_sh, s_cell, in);
+	if (idx < a.P) o = preprocess_one<STAGED, AA>(a, idx, s_sh, s_cell, in);
 	if (a.bucket_count) {
 		// bucket binning (binning.hip): no scan pass runs.  The pair counts per coarse cell were summed in LDS (the Gaussians of an
 		// object are neighbours in index AND on the screen: global atomics serialise on a few hot cells) and go out as this
@@ -208,7 +210,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreprocessArgs a) {
 	}
 }
 
-template <bool STAGED>
+template <bool STAGED, bool AA>
 __device__ __forceinline__ PreOut preprocess_one(const PreprocessArgs& a, const int idx, const float* s_sh, uint32_t* s_cell, const PreIn& in) {
 	const PreOut none = { 0u, 0u };
 	if (idx == 0) {       // sentinels: the exclusive scans over P + 1 entries leave the totals at [P]
@@ -288,6 +290,12 @@ __device__ __forceinline__ PreOut preprocess_one(const PreprocessArgs& a, const 
 
 	Splat s;
 	s.x = pix; s.y = piy; s.ca = conx; s.cb = cony; s.cc = conz; s.opacity = rs ? opacity_in : (STAGED ? in.op : a.opacities[idx]);
+	if (AA) {
+		// opacity-compensated 2D filter: the dilation by 0.3 px^2 widens the footprint by det1 / det0, the opacity shrinks by the square
+		// root of that (clamped at rho = 2.5e-5, k = 0.005).  Everything below -- the Splat's opacity, tau, the lean test -- sees the product.
+		const float det0 = cov.v[0][0] * cov.v[1][1] - cxy * cxy;
+		s.opacity = s.opacity * sqrtf(fmaxf(det0 / det, 2.5e-5f));
+	}
 	uint8_t clamp_bits = 0;
 	if (a.colors_precomp) {
 		s.r = a.colors_precomp[3 * (size_t)idx]; s.g = a.colors_precomp[3 * (size_t)idx + 1]; s.b = a.colors_precomp[3 * (size_t)idx + 2];
@@ -480,11 +488,14 @@ int launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t stream) {
 	if (a.P == 0) return 0;
 	const bool raw = a.sh_src.scene_dc != nullptr;
 	const bool staged = a.M == 16 && !a.colors_precomp && (raw || a.shs) && getenv("ADGS_NO_SH_STAGING") == nullptr;
+	const dim3 grid((a.P + 255) / 256);
 	if (staged) {
 		const size_t lds = (size_t)256 * (raw ? SH_ROW_REST : SH_ROW_FULL_LDS) * sizeof(float);
-		hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3((a.P + 255) / 256), dim3(256), lds, stream, a);
+		if (a.antialias) hipLaunchKernelGGL((preprocess_fwd_kernel<true, true>), grid, dim3(256), lds, stream, a);
+		else hipLaunchKernelGGL((preprocess_fwd_kernel<true, false>), grid, dim3(256), lds, stream, a);
 	} else {
-		hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((a.P + 255) / 256), dim3(256), 0, stream, a);
+		if (a.antialias) hipLaunchKernelGGL((preprocess_fwd_kernel<false, true>), grid, dim3(256), 0, stream, a);
+		else hipLaunchKernelGGL((preprocess_fwd_kernel<false, false>), grid, dim3(256), 0, stream, a);
 	}
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;

@@ -76,7 +76,9 @@ __device__ __forceinline__ PreBIn load_preb_in(const PreprocessBwdArgs& a, const
 	return in;
 }
 
-template <bool STAGED>
+// AA: the frame's forward ran the opacity-compensated 2D filter (PreprocessBwdArgs::antialias) -- a template parameter, so that the
+// instantiations without it are the code they were before the option existed
+template <bool STAGED, bool AA>
 __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBwdArgs a) {
 	extern __shared__ float s_sh[];
 	const int tid = threadIdx.x;
@@ -174,6 +176,7 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 	// per-Gaussian sums of the blend backward: classic = separate ABI arrays filled by atomics,
 	// v2 = one packed 64-byte line per Gaussian, unpacked here into the ABI outputs
 	float dcon_x, dcon_y, dcon_z, g2x, g2y, gd, gcol[3];
+	float aa_g = 0.f, aa_op = 0.f;           // AA: dL/d(effective opacity) and the effective opacity (the blend's `op`)
 	if (a.gacc) {
 		const float4* ga = reinterpret_cast<const float4*>(a.gacc + (size_t)idx * GACC_STRIDE);
 		const float4 u0 = pf ? in.u0 : ga[0], u1 = pf ? in.u1 : ga[1], u2 = pf ? in.u2 : ga[2], u3 = pf ? in.u3 : ga[3];
@@ -189,7 +192,8 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 		gcol[0] = u1.z; gcol[1] = u1.w; gcol[2] = u2.x; gd = u2.y;
 		st_stream(a.out_mean2D + 3 * (size_t)idx, g2x); st_stream(a.out_mean2D + 3 * (size_t)idx + 1, g2y); st_stream(a.out_mean2D + 3 * (size_t)idx + 2, 0.f);
 		if (a.out_conic) *reinterpret_cast<float4*>(a.out_conic + 4 * (size_t)idx) = make_float4(dcon_x, dcon_y, 0.f, dcon_z);
-		if (rs) st_stream(a.sh_dst.scene_opacity + idx, u0.x * act.op * (1.f - act.op));      // d sigmoid
+		if (AA) { aa_g = u0.x; aa_op = op; }      // the opacity gradient is written below, through the filter factor
+		else if (rs) st_stream(a.sh_dst.scene_opacity + idx, u0.x * act.op * (1.f - act.op));      // d sigmoid
 		else st_stream(a.out_opacity + idx, u0.x);
 		if (a.out_color) { a.out_color[3 * (size_t)idx] = gcol[0]; a.out_color[3 * (size_t)idx + 1] = gcol[1]; a.out_color[3 * (size_t)idx + 2] = gcol[2]; }
 		if (a.out_depth) a.out_depth[idx] = gd;
@@ -201,6 +205,7 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 		g2x = a.dL_dmean2D[3 * (size_t)idx]; g2y = a.dL_dmean2D[3 * (size_t)idx + 1];
 		gd = a.dL_ddepth[idx];
 		gcol[0] = a.dL_dcolor[3 * (size_t)idx]; gcol[1] = a.dL_dcolor[3 * (size_t)idx + 1]; gcol[2] = a.dL_dcolor[3 * (size_t)idx + 2];
+		if (AA) { aa_g = a.out_opacity[idx]; aa_op = a.splats[idx].opacity; }      // the blend's atomics are complete: rescaled in place below
 	}
 	// ---------------- cov2D backward (backward.cu:144-274)
 	// in registers either way: a pointer that may refer to a local array would put that array into scratch memory
@@ -233,12 +238,33 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 	const float ca = cov2D.v[0][0] + 0.3f, cb = cov2D.v[0][1], cc = cov2D.v[1][1] + 0.3f;
 	const float denom = ca * cc - cb * cb;
 	float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+	// AA (opacity-compensated 2D filter, preprocess.hip): op_eff = opacity k, k = sqrt(max(rho, 2.5e-5)), rho = det0 / det1 with det0 the
+	// determinant before the 0.3 dilation and det1 = denom after it.  dL/dopacity = g k; dL/drho = g opacity / (2 k) above the clamp
+	float aa_drho = 0.f;
+	if (AA) {
+		const float rho = (cov2D.v[0][0] * cov2D.v[1][1] - cb * cb) / denom;
+		const float k = sqrtf(fmaxf(rho, 2.5e-5f));
+		const float op_in = rs ? act.op : aa_op / k;      // the opacity before the filter (after the sigmoid on raw scene rows)
+		aa_drho = rho > 2.5e-5f ? aa_g * op_in / (2.f * k) : 0.f;
+		if (rs) st_stream(a.sh_dst.scene_opacity + idx, aa_g * k * act.op * (1.f - act.op));      // d sigmoid
+		else if (a.gacc) st_stream(a.out_opacity + idx, aa_g * k);
+		else a.out_opacity[idx] = aa_g * k;
+	}
 	const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
 	float dcov[6];
 	if (denom2inv != 0) {
 		dL_da = denom2inv * (-cc * cc * dcon_x + 2 * cb * cc * dcon_y + (denom - ca * cc) * dcon_z);
 		dL_dc = denom2inv * (-ca * ca * dcon_z + 2 * ca * cb * dcon_y + (denom - ca * cc) * dcon_x);
 		dL_db = denom2inv * 2 * (cb * cc * dcon_x - (denom + 2 * cb * cb) * dcon_y + ca * cb * dcon_z);
+		if (AA) {
+			// drho / d(a, b, c) of the undilated covariance: (c det1 - det0 (c + h)) / det1^2, (a det1 - det0 (a + h)) / det1^2 and
+			// -2 b (det1 - det0) / det1^2, written without their cancellation (det1 - det0 = h (a + c + h), c a - det0 = b^2):
+			// h (c (c + h) + b^2) / det1^2, h (a (a + h) + b^2) / det1^2, -2 b h (a + c + h) / det1^2  (h = 0.3; ca = a + h, cc = c + h)
+			const float q = aa_drho * 0.3f / (denom * denom);
+			dL_da += q * (cov2D.v[1][1] * cc + cb * cb);
+			dL_dc += q * (cov2D.v[0][0] * ca + cb * cb);
+			dL_db += q * (-2.f * cb * (ca + cov2D.v[1][1]));
+		}
 		dcov[0] = (T.v[0][0] * T.v[0][0] * dL_da + T.v[0][0] * T.v[1][0] * dL_db + T.v[1][0] * T.v[1][0] * dL_dc);
 		dcov[3] = (T.v[0][1] * T.v[0][1] * dL_da + T.v[0][1] * T.v[1][1] * dL_db + T.v[1][1] * T.v[1][1] * dL_dc);
 		dcov[5] = (T.v[0][2] * T.v[0][2] * dL_da + T.v[0][2] * T.v[1][2] * dL_db + T.v[1][2] * T.v[1][2] * dL_dc);
@@ -469,11 +495,14 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream) {
 		          "(the frame's forward ran with ADGS_NO_SH_STAGING, or M != 16)");
 		return -1;
 	}
+	if (a.antialias && (!a.out_opacity || (!a.gacc && !a.splats))) { set_error("preprocess backward: the anti-aliased frame's opacity gradient has no destination"); return -1; }
 	if (staged) {
 		const size_t lds = (size_t)BW_THREADS * (raw ? SH_ROW_REST : SH_ROW_FULL_LDS) * sizeof(float);
-		hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3(grid), dim3(BW_THREADS), lds, stream, a);
+		if (a.antialias) hipLaunchKernelGGL((preprocess_bwd_kernel<true, true>), dim3(grid), dim3(BW_THREADS), lds, stream, a);
+		else hipLaunchKernelGGL((preprocess_bwd_kernel<true, false>), dim3(grid), dim3(BW_THREADS), lds, stream, a);
 	} else {
-		hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(grid), dim3(BW_THREADS), 0, stream, a);
+		if (a.antialias) hipLaunchKernelGGL((preprocess_bwd_kernel<false, true>), dim3(grid), dim3(BW_THREADS), 0, stream, a);
+		else hipLaunchKernelGGL((preprocess_bwd_kernel<false, false>), dim3(grid), dim3(BW_THREADS), 0, stream, a);
 	}
 	ADGS_HIP_CHECK(hipGetLastError());
 	// raw-SH path: d/d(shs_deform_param[m, c, k]) = w_k * dL/d(dc[m, c]) as flat coalesced passes

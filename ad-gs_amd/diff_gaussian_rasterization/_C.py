@@ -72,10 +72,12 @@ def _stream_ptr(device):
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, flow_points, semantic,
-                        degree, campos, prefiltered, inv_depth, debug, training=True, plan=None):
+                        degree, campos, prefiltered, inv_depth, debug, training=True, plan=None, antialiasing=False):
     """training=False (extension): the forward-only render, adgs_raster_render -- the same images and radii bit for bit, the three
     state buffers come back as scratch no backward may be run over.  plan (a dict, extension): filled with the validated inputs of this call
-    and their pointers, for rasterize_gaussians_backward(plan=...) of the same call pair (see rasterize_gaussians_rawsh)."""
+    and their pointers, for rasterize_gaussians_backward(plan=...) of the same call pair (see rasterize_gaussians_rawsh).
+    antialiasing (extension): the opacity-compensated 2D filter (include/adgs_rasterizer.h: adgs_raster_options); the backward of the
+    state follows it by itself."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
@@ -113,12 +115,13 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             plan["ptrs"] = tuple(_ptr(t) for t in (bg_, m3_, sh_, col_, fl_, sem_, sc_, rot_, cov_, view_, proj_, cam_))
         try:
             with _on(dev):
-                rendered = _lib.check((lib.adgs_raster_forward if training else lib.adgs_raster_render)(
+                opts = _lib.raster_options(antialiasing)
+                rendered = _lib.check((lib.adgs_raster_forward_opts if training else lib.adgs_raster_render_opts)(
                     geom.cb, geom.user, binning.cb, binning.user, img.cb, img.user, P, int(degree), M, D_S, _ptr(bg_), W, H,
                     _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(fl_), _ptr(sem_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_),
                     _ptr(cov_), _ptr(view_), _ptr(proj_), _ptr(cam_), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
                     _ptr(out_color), _ptr(out_depth), _ptr(img_opacity), _ptr(img_flow), _ptr(img_semantic), int(bool(inv_depth)),
-                    _ptr(radii), int(bool(debug)), _stream_ptr(dev)), "adgs_raster_forward" if training else "adgs_raster_render")
+                    _ptr(radii), int(bool(debug)), _stream_ptr(dev), ctypes.byref(opts)), "adgs_raster_forward_opts" if training else "adgs_raster_render_opts")
         finally:
             for b in (geom, binning, img):
                 b.release()
@@ -243,7 +246,8 @@ def _sh_source(raw, dev):
 
 
 def rasterize_gaussians_rawsh(background, means3D, opacity, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
-                              image_height, image_width, sh_raw, flow_points, semantic, degree, campos, inv_depth, debug, training=True, plan=None):
+                              image_height, image_width, sh_raw, flow_points, semantic, degree, campos, inv_depth, debug, training=True, plan=None,
+                              antialiasing=False):
     """plan (a dict, extension): filled with what the backward of this very call needs again -- the adgs_sh_source struct, the validated
     (contiguous) inputs and their pointers -- so that rasterize_gaussians_backward_rawsh(plan=...) does not validate and marshal them a
     second time (the Python between the loss kernels and the backward's first launch is GPU idle time on a slow host)."""
@@ -284,11 +288,13 @@ def rasterize_gaussians_rawsh(background, means3D, opacity, scales, rotations, s
             plan["ptrs"] = (_ptr(bg_), _ptr(m3_), _ptr(fl_), _ptr(sem_), _ptr(sc_), _ptr(rot_), _ptr(view_), _ptr(proj_), _ptr(cam_))
         try:
             with _on(dev):
-                rendered = _lib.check((lib.adgs_raster_forward_rawsh if training else lib.adgs_raster_render_rawsh)(
+                opts = _lib.raster_options(antialiasing)
+                rendered = _lib.check((lib.adgs_raster_forward_rawsh_opts if training else lib.adgs_raster_render_rawsh_opts)(
                     geom.cb, geom.user, binning.cb, binning.user, img.cb, img.user, P, int(degree), M, D_S, _ptr(bg_), W, H, _ptr(m3_), ctypes.byref(src),
                     _ptr(fl_), _ptr(sem_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(view_), _ptr(proj_), _ptr(cam_),
                     float(tan_fovx), float(tan_fovy), _ptr(out_color), _ptr(out_depth), _ptr(img_opacity), _ptr(img_flow), _ptr(img_semantic),
-                    int(bool(inv_depth)), _ptr(radii), int(bool(debug)), _stream_ptr(dev)), "adgs_raster_forward_rawsh" if training else "adgs_raster_render_rawsh")
+                    int(bool(inv_depth)), _ptr(radii), int(bool(debug)), _stream_ptr(dev), ctypes.byref(opts)),
+                    "adgs_raster_forward_rawsh_opts" if training else "adgs_raster_render_rawsh_opts")
         finally:
             for b in (geom, binning, img):
                 b.release()

@@ -3,7 +3,7 @@
 Same public surface and autograd contract as the reference package
 (submodules/depth-diff-gaussian-rasterization/diff_gaussian_rasterization/__init__.py:21-251):
 
-    GaussianRasterizationSettings   13-field NamedTuple            (ref :176-189)
+    GaussianRasterizationSettings   13-field NamedTuple            (ref :176-189), + `antialiasing` (14th, default False)
     GaussianRasterizer(nn.Module)   .forward(...) -> 6-tuple, .markVisible(...)   (ref :191-251)
     rasterize_gaussians(...)        functional form                 (ref :21-46)
 
@@ -33,6 +33,14 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool
     inv_depth: bool
     debug: bool
+    # extension (upstream 3DGS rasterizers' `antialiasing`): the opacity-compensated 2D filter of Mip-Splatting (include/adgs_rasterizer.h:
+    # adgs_raster_options).  A default, so that the reference's 13-field construction keeps working; train and evaluate with the same value.
+    antialiasing: bool = False
+
+
+def _antialiasing(settings):
+    """The settings' anti-aliasing flag (False for a settings object of the reference's 13 fields)."""
+    return bool(getattr(settings, "antialiasing", False))
 
 
 def _snapshot(args):
@@ -65,8 +73,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                        s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, flow_points,
                        semantic, s.sh_degree, s.campos, s.prefiltered, s.inv_depth, s.debug)
         plan = {}      # the validated inputs / pointers of this call, for its backward (_C.rasterize_gaussians)
+        aa = _antialiasing(s)
         (num_rendered, color, depth, img_opacity, radii, geom_buf, binning_buf, img_buf, img_flow,
-         img_semantic) = _call_with_dump(lambda *a: _C.rasterize_gaussians(*a, plan=plan), native_args, s.debug, "snapshot_fw.dump", "forward")
+         img_semantic) = _call_with_dump(lambda *a: _C.rasterize_gaussians(*a, plan=plan, antialiasing=aa), native_args, s.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings, ctx.plan = s, plan
         ctx.num_rendered = num_rendered
         ctx.set_materialize_grads(False)     # outputs the loss does not use arrive as None (NULL for the kernels), not as zero fills
@@ -131,7 +140,7 @@ class _RasterizeGaussiansRawSH(torch.autograd.Function):
         plan = {}      # the validated inputs / pointers / adgs_sh_source of this call, for its backward (_C.rasterize_gaussians_rawsh)
         (num_rendered, color, depth, img_opacity, radii, geom_buf, binning_buf, img_buf, img_flow, img_semantic) = _C.rasterize_gaussians_rawsh(
             s.bg, means3D, opacities, scales, rotations, s.scale_modifier, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height,
-            s.image_width, raw, flow_points, semantic, s.sh_degree, s.campos, s.inv_depth, s.debug, plan=plan)
+            s.image_width, raw, flow_points, semantic, s.sh_degree, s.campos, s.inv_depth, s.debug, plan=plan, antialiasing=_antialiasing(s))
         ctx.raster_settings, ctx.num_rendered, ctx.func_eval, ctx.factor_sink, ctx.plan = s, num_rendered, func_eval, factor_sink, plan
         ctx.has_geo, ctx.grad_arena, ctx.has_bg, ctx.adam = geo is not None, grad_arena, bg_image is not None, adam
         ctx.set_materialize_grads(False)
@@ -188,7 +197,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp, s.viewmatrix, s.projmatrix, s.tanfovx,
                 s.tanfovy, s.image_height, s.image_width, sh, flow_points, semantic, s.sh_degree, s.campos, s.prefiltered, s.inv_depth, s.debug)
         with torch.no_grad():
-            r = _call_with_dump(lambda *a: _C.rasterize_gaussians(*a, training=False), args, s.debug, "snapshot_fw.dump", "forward")
+            r = _call_with_dump(lambda *a: _C.rasterize_gaussians(*a, training=False, antialiasing=_antialiasing(s)), args, s.debug, "snapshot_fw.dump", "forward")
         return r[1], r[4], r[2], r[3], r[8], r[9]
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      flow_points, semantic, raster_settings)
@@ -220,7 +229,7 @@ class GaussianRasterizer(nn.Module):
             with torch.no_grad():
                 r = _C.rasterize_gaussians_rawsh(s.bg, means3D, opacities, scales, rotations, s.scale_modifier, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
                                                  s.image_height, s.image_width, raw, empty(flow_points), empty(semantic), s.sh_degree, s.campos, s.inv_depth,
-                                                 s.debug, training=False)
+                                                 s.debug, training=False, antialiasing=_antialiasing(s))
             return r[1], r[4], r[2], r[3], r[8], r[9]
         return _RasterizeGaussiansRawSH.apply(means3D, means2D, opacities, scales, rotations, empty(flow_points), empty(semantic),
                                               sh_raw.scene_dc, sh_raw.obj_dc, sh_raw.scene_rest, sh_raw.obj_rest, sh_raw.scene_deform,

@@ -48,7 +48,8 @@ def _camera_settings(cam, pc, pipe, scale_modifier, device):
     view, proj, center = _camera_matrices(cam, device)
     return GaussianRasterizationSettings(
         int(cam.image_height), int(cam.image_width), math.tan(0.5 * cam.FoVx), math.tan(0.5 * cam.FoVy),
-        black, scale_modifier, view, proj, pc.active_sh_degree, center, False, pipe.inv_depth, pipe.debug)
+        black, scale_modifier, view, proj, pc.active_sh_degree, center, False, pipe.inv_depth, pipe.debug,
+        bool(getattr(pipe, "antialiasing", False)))      # upstream's PipelineParams.antialiasing; a pipe without it renders without the filter
 
 
 def _deformed_state(pc, t, flow_pkg, full_rows=False):

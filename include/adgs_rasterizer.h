@@ -183,8 +183,9 @@ typedef struct adgs_sh_source {
 } adgs_sh_source;
 struct adgs_sh_adam;      /* adgs_optim.h */
 typedef struct adgs_sh_grads {
-	uint64_t struct_bytes;   /* sizeof(adgs_sh_grads) as the CALLER was compiled: members beyond it are taken as NULL, so a caller built against an
-	                            older header (before `adam`) keeps working; 0 or less than the first seven pointers is an error */
+	uint64_t struct_bytes;   /* sizeof(adgs_sh_grads) as the CALLER was compiled: members beyond it are taken as NULL (growth at the end only).
+	                            Inserting this member first was itself an ABI break: a caller built against a header without it is refused
+	                            (0, less than the first seven pointers, or more than 4096 is an error), it does not keep working */
 	float *scene_dc, *obj_dc, *scene_rest, *obj_rest, *scene_deform, *obj_deform;   /* NULL = not wanted */
 	float *rgb_factor;   /* [P,3] or NULL: the clamp-masked colour gradient dL/dRGB * (1 - clamped) (backward.cu:20-139), 0 for
 	                        Gaussians with radii == 0 -- the one per-camera vector every SH gradient row above is a multiple of
@@ -238,6 +239,57 @@ int adgs_raster_backward_rawsh(
  * must stay zero-filled when the corresponding input is absent: out_color (no shs/colours),
  * img_flow / dL_dflow (no flow_points), dL_dscale / dL_drot (cov3D_precomp given). */
 int adgs_raster_needs_zero_init(int D_S);
+
+/* Options of a forward (the `_opts` entries below).  Versioned by its size: set struct_bytes = sizeof(adgs_raster_options) of the
+ * header the caller was compiled against.  The library reads min(struct_bytes, its own sizeof) bytes; members a LATER header appends
+ * keep their defaults for a caller that did not know them.  A struct_bytes that does not reach `antialiasing` (or exceeds 4096) is
+ * refused.  Only growth at the end is covered: a member inserted or reordered is a break of this ABI, not a compatible change.
+ * A NULL options pointer means the defaults (all members 0). */
+typedef struct adgs_raster_options {
+	uint64_t struct_bytes;
+	/* 1: anti-aliased splatting, the opacity-compensated 2D filter of Mip-Splatting (upstream 3DGS rasterizers' `antialiasing`).  With
+	 * a = Sigma2D[0][0], b = Sigma2D[0][1], c = Sigma2D[1][1] the screen-space covariance BEFORE the 0.3 px^2 dilation,
+	 * rho = (a c - b^2) / ((a + 0.3)(c + 0.3) - b^2) and k = sqrt(max(rho, 2.5e-5)), every use of the opacity after the projection takes
+	 * opacity * k (raw scene rows: after the sigmoid).  Radii and tile rectangles are those of the dilated covariance, as without it;
+	 * num_rendered can only go down.  The backward of the frame differentiates through k -- it follows its FORWARD's setting (recorded
+	 * in the state buffers), it takes no option itself.  Train and evaluate a model with the same setting.  0 (default): off. */
+	int32_t antialiasing;
+} adgs_raster_options;
+
+/* adgs_raster_forward / adgs_raster_render / adgs_raster_forward_rawsh / adgs_raster_render_rawsh with options: the same arguments and
+ * a trailing `options` (NULL = the defaults; the four entries above are these with NULL). */
+int adgs_raster_forward_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options);
+int adgs_raster_render_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options);
+int adgs_raster_forward_rawsh_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options);
+int adgs_raster_render_rawsh_opts(
+	adgs_alloc_fn geometryBuffer, void* geometryUser, adgs_alloc_fn binningBuffer, void* binningUser, adgs_alloc_fn imageBuffer, void* imageUser,
+	int P, int D, int M, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
+	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options);
 /* ... and for the backward of a given forward (its state buffers, shape and point count): what THAT forward's pipeline needs, from the
  * library's frame table -- the backward never consults the environment.  Unknown state: 1 (zero-fill is always safe). */
 int adgs_raster_backward_needs_zero_init(const char* geom_buffer, const char* img_buffer, int width, int height, int P);
