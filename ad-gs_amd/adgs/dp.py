@@ -97,6 +97,19 @@ def allreduce_densification_stats(xyz_gradient_accum, denom, max_radii2D, group=
     dist.all_reduce(max_radii2D, op=dist.ReduceOp.MAX, group=group)
 
 
+def allreduce_visibility(visibility, group=None):
+    """The visibility of a data-parallel step (FusedAdam.step(visibility=...)): every replica must mask the same rows, so the union of
+    what the ranks' cameras saw -- the element-wise maximum of their radii -- replaces each rank's own, in place."""
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return visibility
+    if visibility.dtype == torch.bool:
+        as_bytes = visibility.view(torch.uint8)          # same storage: the collectives have no boolean maximum
+        dist.all_reduce(as_bytes, op=dist.ReduceOp.MAX, group=group)
+    else:
+        dist.all_reduce(visibility, op=dist.ReduceOp.MAX, group=group)
+    return visibility
+
+
 def seed_all_ranks(seed, group=None):
     """Densify draws torch.normal / randperm (scene/gaussian_model.py:720,731,832): every replica
     must draw the same samples, so rank 0's seed is broadcast and applied everywhere."""

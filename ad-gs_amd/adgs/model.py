@@ -135,12 +135,15 @@ class SyntheticGaussianModel:
     percent_dense, scene_extent, object_extent = 0.01, 1.0, 1.0
     use_near_idx, near_num, obj_near_idx, optimizer = False, 0, None, None
 
-    def training_setup(self, lrs=None, percent_dense=0.01, scene_extent=None, object_extent=None, near_num=0, adam_in_backward=False):
+    def training_setup(self, lrs=None, percent_dense=0.01, scene_extent=None, object_extent=None, near_num=0, adam_in_backward=False, sparse_adam=False):
         """The optimizer of GaussianModel.training_setup (:338-372): one group per raw tensor, the reference's group names,
         Adam(lr=0, eps=1e-15) -- here the fused HIP Adam.  `lrs`: {group name: lr} (default 1e-3 each).
         adam_in_backward: FusedAdam(in_backward=True) -- optimizer.arm_backward() then lets the rasterizer's backward apply the step
-        of the SH rest / SH deformation tensors itself (adgs.optim.BackwardEpilogue)."""
-        from .optim import FusedAdam
+        of the SH rest / SH deformation tensors itself (adgs.optim.BackwardEpilogue).
+        sparse_adam: marks the per-Gaussian groups for the visibility-masked step (adgs.optim.mark_visibility_groups: everything but
+        deform_xyz, time_sigma and deform_background) -- optimizer.step(visibility=render_pkg["radii"]) then steps only the
+        Gaussians the camera saw; without `visibility=` the step stays dense."""
+        from .optim import FusedAdam, mark_visibility_groups
         lrs = lrs or {}
         self.percent_dense = percent_dense
         self.scene_extent = self.scene_extent if scene_extent is None else scene_extent
@@ -162,6 +165,8 @@ class SyntheticGaussianModel:
                 setattr(self, attr, t)
             groups.append({"params": [t], "lr": float(lrs.get(name, 1e-3)), "name": name})
         self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15, in_backward=bool(adam_in_backward))
+        if sparse_adam:
+            mark_visibility_groups(self.optimizer)
         self.near_num, self.use_near_idx = near_num, near_num > 0
         self.set_obj_near_idx()
         return self.optimizer

@@ -9,6 +9,10 @@ schedulers that write `group['lr']` keep working) and the same per-parameter sta
 
 All groups are updated by ONE kernel launch (adgs_adam_step, include/adgs_optim.h); parameters
 without a gradient are skipped exactly like torch does.  There is no CPU fallback.
+
+Opt-in: the visibility-masked ("sparse") step of upstream 3DGS's `--optimizer_type sparse_adam` --
+`step(visibility=radii)` updates, in the groups marked with `group["visibility_rows"]`, only the rows the
+iteration's render saw (adgs_adam_step_rows); see FusedAdam.step and mark_visibility_groups.
 """
 import ctypes
 
@@ -35,6 +39,15 @@ class ShAdam(ctypes.Structure):
     _fields_ = [(n, AdamSlot) for n in ("scene_rest", "obj_rest", "scene_deform", "obj_deform")] + \
                [("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
+
+class AdamRows(ctypes.Structure):
+    """adgs_adam_rows (include/adgs_optim.h)."""
+    _fields_ = [("visible", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("row_len", ctypes.c_int32), ("kind", ctypes.c_int32)]
+
+
+ROWS_DENSE, ROWS_INT32, ROWS_UINT8 = 0, 1, 2        # adgs_adam_rows.kind
+_VISIBILITY_KINDS = {torch.int32: ROWS_INT32, torch.bool: ROWS_UINT8, torch.uint8: ROWS_UINT8}
+VISIBILITY_ROWS = ("head", "tail")                  # param_groups[i]["visibility_rows"]; absent / None: dense
 
 ADAM_TILE = 256            # ADGS_ADAM_TILE
 TILES_MARKED, ZERO_GRAD = 1, 2          # adgs_adam_group.flags
@@ -222,9 +235,65 @@ class FusedAdam(torch.optim.Optimizer):
             mg = self._marked[id(p)] = MarkedGradient(self._tile_maps[id(p)][0])
         return mg
 
+    @staticmethod
+    def _check_visibility(visibility):
+        """step(visibility=...): what can be said about the tensor alone, before anything else happens; returns its adgs_adam_rows.kind."""
+        if not torch.is_tensor(visibility) or visibility.dim() != 1:
+            raise ValueError("FusedAdam.step(visibility=): one 1-D tensor with an entry per Gaussian (the radii of the render)")
+        kind = _VISIBILITY_KINDS.get(visibility.dtype)
+        if kind is None:
+            raise ValueError("FusedAdam.step(visibility=): int32 (radii, visible iff > 0), bool or uint8 (visible iff != 0); got %s" % visibility.dtype)
+        if not visibility.is_cuda:
+            raise ValueError("FusedAdam.step(visibility=): the visibility must live on the HIP device of the parameters; there is no CPU path")
+        if not visibility.is_contiguous():
+            raise ValueError("FusedAdam.step(visibility=): the visibility must be contiguous")
+        return kind
+
+    def _visibility_rows(self, visibility, kind):
+        """step(visibility=...): checks every masked group against the visibility BEFORE anything is stepped -- and AFTER the closure, which
+        is what produces the gradients (and may run an armed backward); returns id(param) -> AdamRows for the parameters of masked groups
+        that have a gradient."""
+        if self.backward_epilogue is not None and self.backward_epilogue.claimed:
+            raise RuntimeError("FusedAdam.step(visibility=): this iteration's rasterizer backward has already stepped the SH tensors densely "
+                               "(arm_backward()); the in-backward step and the visibility-masked step cannot be mixed")
+        N, rows, sizes = visibility.numel(), {}, {"head": set(), "tail": set()}
+        for group in self.param_groups:
+            where = group.get("visibility_rows")
+            if where is None:
+                continue
+            if where not in VISIBILITY_ROWS:
+                raise ValueError("FusedAdam: group['visibility_rows'] must be 'head', 'tail' or None, got %r" % (where,))
+            if self.skip_dormant_tiles:
+                raise ValueError("FusedAdam.step(visibility=): a group marked for the masked step in an optimizer with skip_dormant_tiles "
+                                 "(the dormant-tile map and the row visibility cannot be combined)")
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.dim() < 1 or p.shape[0] > N:
+                    raise ValueError("FusedAdam.step(visibility=): group %r has %s rows, the visibility %d entries"
+                                     % (group.get("name"), p.shape[0] if p.dim() else "no", N))
+                if p.device != visibility.device:
+                    raise ValueError("FusedAdam.step(visibility=): group %r lives on %s, the visibility on %s" % (group.get("name"), p.device, visibility.device))
+                R = int(p.shape[0])
+                offset = 0 if where == "head" else N - R
+                rows[id(p)] = AdamRows(visibility.data_ptr() + offset * visibility.element_size(), R, p.numel() // R if R else 1, kind)
+                sizes[where].add(R)
+        if len(sizes["head"]) == 1 and len(sizes["tail"]) == 1 and sum(sizes["head"]) + sum(sizes["tail"]) != N:
+            # a model's optimizer (every head group has the scene's rows, every tail group the objects'): the visibility must be this
+            # model's -- radii from before a densification would make the tail groups read the wrong slice
+            raise ValueError("FusedAdam.step(visibility=): the head groups have %d rows and the tail groups %d, the visibility has %d entries, "
+                             "not their sum (radii of a render from before a densification?)" % (sum(sizes["head"]), sum(sizes["tail"]), N))
+        return rows
+
     @torch.no_grad()
-    def step(self, closure=None, zero_grad=False):
+    def step(self, closure=None, zero_grad=False, visibility=None):
         """One Adam step over every parameter that has a gradient.
+        visibility: one device tensor with an entry per Gaussian in the rasterizer's row order (scene rows first, object rows last) --
+        normally the `radii` of the iteration's render (int32, visible iff > 0; bool / uint8: visible iff != 0; several cameras:
+        merge_visibility).  In the groups marked group["visibility_rows"] = "head" | "tail" (mark_visibility_groups; the group's
+        rows are the first / the last p.shape[0] entries of the visibility) only visible rows are stepped: an invisible row keeps its
+        parameter and both moments bit for bit and its gradient is not read.  Visible rows, and every group that is not marked, take
+        the dense update in the same launch; `state['step']` stays one counter per tensor.  None: the dense step, as ever.
         zero_grad=True: the reference's `optimizer.zero_grad(set_to_none=True)` right after the step (train.py:165) -- the
         gradients are dropped (`p.grad = None`), so a parameter that receives no gradient in a later iteration is skipped by the
         next step exactly as torch.optim.Adam skips it (no moment-driven update, `step` not incremented).
@@ -233,10 +302,12 @@ class FusedAdam(torch.optim.Optimizer):
         if zero_grad not in (False, True, "zeros"):
             raise ValueError("zero_grad must be False, True (set to None) or 'zeros' (zero-fill in place)")
         fill = zero_grad == "zeros"
+        kind = None if visibility is None else self._check_visibility(visibility)
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        rows = None if visibility is None else self._visibility_rows(visibility, kind)      # the gradients exist now
         if self.backward_epilogue is not None:
             epi = self.backward_epilogue
             for p in epi.claimed:
@@ -291,6 +362,10 @@ class FusedAdam(torch.optim.Optimizer):
                                int(st["step"]), tile_map.data_ptr() if tile_map is not None else None, flags, 0)
                 keep.append(g)
                 batches.setdefault((p.device, float(b1), float(b2), float(group["eps"])), []).append((ag, p, g))
+                if rows is not None and id(p) not in rows:
+                    if group.get("visibility_rows") is not None:     # cannot happen: _visibility_rows saw every gradient this loop sees
+                        raise RuntimeError("FusedAdam.step(visibility=): group %r is marked for the masked step but has no row table" % (group.get("name"),))
+                    rows[id(p)] = AdamRows(None, 0, 1, ROWS_DENSE)
         lib = _lib.lib()
         for (dev, b1, b2, eps), items in batches.items():
             with torch.cuda.device(dev):
@@ -298,7 +373,11 @@ class FusedAdam(torch.optim.Optimizer):
                 for i in range(0, len(items), MAX_GROUPS):
                     chunk = items[i:i + MAX_GROUPS]
                     arr = (AdamGroup * len(chunk))(*[c[0] for c in chunk])
-                    _lib.check(lib.adgs_adam_step(arr, len(chunk), b1, b2, eps, int(fill), stream), "adgs_adam_step")
+                    if rows is None:
+                        _lib.check(lib.adgs_adam_step(arr, len(chunk), b1, b2, eps, int(fill), stream), "adgs_adam_step")
+                    else:
+                        vis = (AdamRows * len(chunk))(*[rows[id(c[1])] for c in chunk])
+                        _lib.check(lib.adgs_adam_step_rows(arr, vis, len(chunk), b1, b2, eps, int(fill), stream), "adgs_adam_step_rows")
             for _, p, g in items:
                 if fill and g is not p.grad:
                     p.grad.zero_()          # the kernel zeroed the contiguous copy
@@ -307,6 +386,40 @@ class FusedAdam(torch.optim.Optimizer):
         for mg, g in recycle:
             mg.buffer = g
         return loss
+
+
+def mark_visibility_groups(optimizer, dense=("deform_xyz", "time_sigma", "deform_background")):
+    """Marks the param_groups of a GaussianModel's optimizer (the reference's group names: adgs.densify.GROUP_ATTR) for the
+    visibility-masked step: `scene_*` and `deform_shs_scene` hold the scene rows, the head of the rasterizer's row order;
+    `obj_*`, `deform_shs_obj`, `deform_rotation`, `deform_xyz` and `time_sigma` hold the object rows, its tail.  Which END is
+    stored, not an offset, so the mark survives densification (the tensors and both row counts change, the group dicts stay).
+    `dense`: groups that keep the dense step.  The default leaves out `deform_xyz` and `time_sigma`, whose regularisers
+    (reg_loss / sigma_loss / reg_sigma_loss, train.py:101-110) give every row a gradient that has nothing to do with what the
+    camera saw, and `deform_background`, which has one row.  Groups with other names are left as they are.  Returns the
+    {name: mark} it set."""
+    from .densify import SCENE_GROUPS, OBJ_GROUPS
+    marks = {}
+    for group in optimizer.param_groups:
+        name = group.get("name")
+        if name in dense:
+            where = None
+        elif name in SCENE_GROUPS:
+            where = "head"
+        elif name in OBJ_GROUPS:
+            where = "tail"
+        else:
+            continue
+        group["visibility_rows"] = marks[name] = where
+    return marks
+
+
+def merge_visibility(acc, radii):
+    """The visibility of a step that accumulates several cameras: the union of what they saw, i.e. the element-wise maximum of
+    their `radii` (or masks).  acc: the running union, None for the first camera; returns the new union (its own tensor; later
+    calls update it in place)."""
+    if acc is None:
+        return radii.detach().clone()
+    return torch.maximum(acc, radii, out=acc)
 
 
 def add_densification_stats(xyz_gradient_accum, denom, max_radii2D, viewspace_grad, radii):

@@ -1454,6 +1454,7 @@ extern "C" size_t adgs_test_abi_sizeof(int which) {
 	case 5: return sizeof(adgs_adam_group);
 	case 6: return sizeof(adgs_sh_adam);
 	case 7: return sizeof(adgs_raster_options);
+	case 8: return sizeof(adgs_adam_rows);
 	default: return 0;
 	}
 }

@@ -53,6 +53,26 @@ typedef struct adgs_adam_group {
  * code with adgs_last_error() set. */
 int adgs_adam_step(const adgs_adam_group* groups, int n_groups, float beta1, float beta2, float eps, int zero_grad, void* stream);
 
+/* The visibility-masked ("sparse") step: upstream 3DGS's `--optimizer_type sparse_adam`.  rows[i] (parallel to groups, NULL = every
+ * group dense) views group i as [n_rows, row_len] and names one visibility value per row -- normally a slice of the radii the
+ * iteration's render returned.  A visible row takes exactly the update of adgs_adam_step (bias corrections from the group's own
+ * `step`, unlike upstream's kernel, which has none: with every row visible the two entries give the same bits).  A row that is
+ * not visible keeps the bits of its parameter AND of both moments, and its gradient is not read, whatever it holds; it is still
+ * zeroed when zero_grad (or ADGS_ADAM_ZERO_GRAD) asks for a fill.  Groups of kind ADGS_ADAM_ROWS_DENSE take the dense step in
+ * the same launch.  Rejected (negative code, adgs_last_error()): n_rows * row_len != numel, row_len < 1, an unknown kind, a
+ * masked group that also has a tile_active map.  One launch, no host synchronisation, no allocation: capturable in a HIP graph. */
+typedef struct adgs_adam_rows {
+	const void* visible;    /* device pointer, already offset to the group's first row; n_rows entries */
+	int64_t n_rows;
+	int32_t row_len;
+	int32_t kind;           /* ADGS_ADAM_ROWS_* */
+} adgs_adam_rows;
+#define ADGS_ADAM_ROWS_DENSE 0      /* no visibility: the dense step (visible is ignored) */
+#define ADGS_ADAM_ROWS_INT32 1      /* int32 per row, visible iff > 0 (radii; negative = not visible) */
+#define ADGS_ADAM_ROWS_UINT8 2      /* one byte per row, visible iff != 0 (bool / uint8 masks) */
+int adgs_adam_step_rows(const adgs_adam_group* groups, const adgs_adam_rows* rows, int n_groups, float beta1, float beta2, float eps, int zero_grad,
+	void* stream);
+
 /* The same step applied INSIDE the rasterizer's backward (adgs_sh_grads.adam, adgs_rasterizer.h), for the single-camera iteration
  * of train.py:47-167 (one backward, then optimizer.step() -- :163-167).  The kernels that produce the gradient of a raw SH tensor
  * hold each element of it in a register or in LDS exactly once: they read (p, m, v), apply the update above and write (p, m, v)
