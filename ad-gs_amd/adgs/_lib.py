@@ -43,6 +43,13 @@ SIGNATURES = {
     "adgs_raster_backward_rawsh": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p,
                                          c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
+    # the two backward entries with a trailing const adgs_raster_backward_options* (NULL = the defaults)
+    "adgs_raster_backward_opts": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p,
+                                        c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "adgs_raster_backward_rawsh_opts": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p,
+                                              c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                              c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     # the four forward entries with a trailing const adgs_raster_options* (NULL = the defaults)
     "adgs_raster_forward_opts": (c_i, [ALLOC_FN, c_p, ALLOC_FN, c_p, ALLOC_FN, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i,
                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i,
@@ -140,6 +147,20 @@ def raster_options(antialiasing=False):
     o = RasterOptions()
     o.struct_bytes = ctypes.sizeof(RasterOptions)
     o.antialiasing = 1 if antialiasing else 0
+    return o
+
+
+class RasterBackwardOptions(ctypes.Structure):
+    """adgs_raster_backward_options (include/adgs_rasterizer.h); struct_bytes is filled in by raster_backward_options()."""
+    _fields_ = [("struct_bytes", ctypes.c_uint64), ("dL_dmean2D_abs", ctypes.c_void_p)]
+
+
+def raster_backward_options(dL_dmean2D_abs=None):
+    """An adgs_raster_backward_options for the `_opts` backward entries; dL_dmean2D_abs: the data pointer of a contiguous fp32 [P,3]
+    tensor that receives the absolute screen-space gradient sums, or None (not asked)."""
+    o = RasterBackwardOptions()
+    o.struct_bytes = ctypes.sizeof(RasterBackwardOptions)
+    o.dL_dmean2D_abs = dL_dmean2D_abs
     return o
 
 

@@ -173,7 +173,10 @@ class SyntheticGaussianModel:
 
     def add_densification_stats(self, render_pkg):
         from .optim import add_densification_stats
-        add_densification_stats(self.xyz_gradient_accum, self.denom, self.max_radii2D, render_pkg["viewspace_points"].grad, render_pkg["radii"])
+        # a render with pipe.absgrad hands out a second leaf: the absolute screen-space gradient sums replace the signed ones in the ONE
+        # accumulator (gsplat's absgrad semantics; the thresholds are the caller's)
+        leaf = render_pkg["viewspace_points_abs"] if "viewspace_points_abs" in render_pkg else render_pkg["viewspace_points"]
+        add_densification_stats(self.xyz_gradient_accum, self.denom, self.max_radii2D, leaf.grad, render_pkg["radii"])
 
     def densify_and_prune(self, max_scene_grad, max_obj_grad, min_opacity, prune_big_points):
         info = _densify.densify_and_prune(self, max_scene_grad, max_obj_grad, min_opacity, prune_big_points)

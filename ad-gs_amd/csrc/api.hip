@@ -968,10 +968,18 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 	const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_flow, const float* dL_dpix_semantic,
 	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
 	float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
-	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream_) {
+	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream_, float* dL_dmean2D_abs = nullptr) {
 	hipStream_t stream = (hipStream_t)stream_;
 	if (P <= 0) return 0;
 	if (!geom_buffer || !img_buffer || (R > 0 && !binning_buffer)) { set_error("backward called without forward state buffers"); return -1; }
+	// The absolute-gradient request (adgs_raster_backward_options) is settled before the first launch.  More than one semantic channel with a
+	// semantic gradient: channels 1.. are replayed by passes of their own that add their share of dL/dalpha to the accumulator lines, and a
+	// sum of per-pass absolutes is not the absolute of the pair's term.
+	if (dL_dmean2D_abs && dL_dpix_semantic && semantic && D_S > 1) {
+		set_error("backward: dL_dmean2D_abs cannot be computed with D_S > 1 semantic channels and a semantic gradient (the extra channels are separate replays: "
+		          "their per-pass absolute sums are not the absolute of the pair's term)");
+		return -1;
+	}
 	const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
 	const size_t ntiles = (size_t)gx * gy, npix = (size_t)width * height;
 	FrameCfg cfg;
@@ -987,6 +995,11 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		ADGS_HIP_CHECK(hipMemcpyAsync(&word, img_buffer, sizeof(word), hipMemcpyDeviceToHost, stream));
 		ADGS_HIP_CHECK(hipStreamSynchronize(stream));
 		if (!frame_cfg_from_word(word, &cfg)) { set_error("backward: the image state buffer does not carry a forward's configuration word (not written by adgs_raster_forward?)"); return -1; }
+	}
+	if (dL_dmean2D_abs && !cfg.v2) {
+		set_error("backward: dL_dmean2D_abs needs a forward of the default (v2) pipeline; this frame's forward ran the classic pipeline "
+		          "(ADGS_RASTER_MODE=classic, or D_S above ADGS_V2_MAX_SEMANTIC), which does not form the absolute sums");
+		return -1;
 	}
 	if (cfg.v2) {
 		const int cell_tiles = cfg.cell_tiles;
@@ -1010,6 +1023,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		ra.do_sem = dL_dpix_semantic && semantic && D_S > 0;
 		ra.do_depth = dL_dpix_depth != nullptr;
 		ra.do_opacity = grad_img_opacity != nullptr || (ra.bg_image != nullptr && ra.do_color);      // the per-pixel background's term rides on the opacity path
+		ra.absgrad = dL_dmean2D_abs != nullptr;
 		ra.gacc = geom.gacc;
 		ra.tile_order = nullptr;
 		ra.tl_start = cfg.timeline ? img.tile_scanned : nullptr; ra.tl_end = img.tile_batches;      // experiment build only
@@ -1033,7 +1047,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 				// by the preprocess backward with every other output row)
 				ADGS_HIP_CHECK(hipMemsetAsync(dL_dsemantic, 0, (size_t)P * D_S * sizeof(float), stream));
 				RenderV2BwdArgs rc = ra;
-				rc.do_color = rc.do_flow = rc.do_depth = rc.do_opacity = false; rc.do_sem = true;
+				rc.do_color = rc.do_flow = rc.do_depth = rc.do_opacity = false; rc.do_sem = true; rc.absgrad = false;      // (refused above when asked for)
 				rc.dL_dpix = nullptr; rc.dL_dpix_depth = nullptr; rc.dL_dpix_flow = nullptr; rc.dL_dpix_opacity = nullptr;
 				rc.bg_image = nullptr; rc.dL_dbg_image = nullptr; rc.sem_stride = D_S;
 				for (int c = 1; c < D_S; c++) {
@@ -1058,6 +1072,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		if (sh_src) { pa.sh_src = *sh_src; if (sh_dst) pa.sh_dst = *sh_dst; }
 		pa.out_mean2D = dL_dmean2D; pa.out_conic = dL_dconic; pa.out_opacity = dL_dopacity; pa.out_color = dL_dcolor; pa.out_depth = dL_ddepth;
 		pa.out_flow = ra.do_flow ? dL_dflow : nullptr; pa.out_sem = ra.do_sem ? dL_dsemantic : nullptr; pa.D_S = D_S;
+		pa.out_mean2D_abs = dL_dmean2D_abs;
 		pa.sh_staging = cfg.sh_staging;
 		pa.ddir = geom.ddir;
 		pa.antialias = cfg.antialiasing;
@@ -1103,7 +1118,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 	if (sh_src) { set_error("the raw-SH entry points need the default (v2) pipeline (not ADGS_RASTER_MODE=classic, D_S <= ADGS_V2_MAX_SEMANTIC)"); return -1; }
 	memset(&pa.sh_src, 0, sizeof(pa.sh_src)); pa.sh_dst = ShGradDst{};
 	pa.gacc = nullptr; pa.splats = nullptr; pa.W = width; pa.H = height; pa.out_mean2D = nullptr; pa.out_conic = nullptr; pa.out_opacity = nullptr; pa.out_color = nullptr; pa.out_depth = nullptr;
-	pa.out_flow = nullptr; pa.out_sem = nullptr; pa.D_S = D_S;
+	pa.out_flow = nullptr; pa.out_sem = nullptr; pa.D_S = D_S; pa.out_mean2D_abs = nullptr;
 	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr;
 	// anti-aliased frame: the blend's atomics left dL/d(effective opacity) in dL_dopacity; the preprocess backward rescales it in place and
 	// reads the effective opacity from the Splat lines
@@ -1185,6 +1200,38 @@ extern "C" int adgs_raster_render(
 	return adgs_raster_render_opts(geometryBuffer, geometryUser, binningBuffer, binningUser, imageBuffer, imageUser, P, D, M, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, img_opacity, img_flow, img_semantic, inv_depth, radii, debug, stream, nullptr);
 }
 
+// adgs_raster_backward_options (include/adgs_rasterizer.h), read like adgs_raster_options: NULL = the defaults
+static int read_backward_options(const adgs_raster_backward_options* o, const char* who, float** dL_dmean2D_abs) {
+	*dL_dmean2D_abs = nullptr;
+	if (!o) return 0;
+	if (o->struct_bytes < offsetof(adgs_raster_backward_options, dL_dmean2D_abs) + sizeof(float*) || o->struct_bytes > 4096) {
+		set_error(std::string(who) + ": adgs_raster_backward_options.struct_bytes must be sizeof(adgs_raster_backward_options) of the caller's header"); return -1;
+	}
+	adgs_raster_backward_options full;
+	memset(&full, 0, sizeof(full));
+	memcpy(&full, o, std::min<size_t>((size_t)o->struct_bytes, sizeof(full)));
+	*dL_dmean2D_abs = full.dL_dmean2D_abs;
+	return 0;
+}
+
+extern "C" int adgs_raster_backward_opts(
+	int P, int D, int M, int R, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+	const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+	const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_flow, const float* dL_dpix_semantic,
+	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
+	float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
+	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream, const adgs_raster_backward_options* options) {
+	float* abs_dst = nullptr;
+	if (read_backward_options(options, "adgs_raster_backward_opts", &abs_dst) != 0) return -1;
+	return raster_backward_impl(nullptr, nullptr, P, D, M, R, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic,
+		scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+		img_buffer, dL_dpix, dL_dpix_depth, dL_dpix_flow, dL_dpix_semantic, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D,
+		dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dflow, dL_dsemantic, grad_img_opacity, img_opacity, inv_depth, debug, stream, abs_dst);
+}
+
 extern "C" int adgs_raster_backward(
 	int P, int D, int M, int R, int D_S, const float* background, int width, int height,
 	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
@@ -1195,10 +1242,10 @@ extern "C" int adgs_raster_backward(
 	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
 	float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
 	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream) {
-	return raster_backward_impl(nullptr, nullptr, P, D, M, R, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic,
+	return adgs_raster_backward_opts(P, D, M, R, D_S, background, width, height, means3D, shs, colors_precomp, flow_points, semantic,
 		scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
 		img_buffer, dL_dpix, dL_dpix_depth, dL_dpix_flow, dL_dpix_semantic, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D,
-		dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dflow, dL_dsemantic, grad_img_opacity, img_opacity, inv_depth, debug, stream);
+		dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dflow, dL_dsemantic, grad_img_opacity, img_opacity, inv_depth, debug, stream, nullptr);
 }
 
 // scene_dc != NULL is what switches the kernels to the raw-SH source, and an empty side (a model without scene or without
@@ -1297,6 +1344,24 @@ extern "C" int adgs_raster_backward_rawsh(
 	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
 	float* dL_dcov3D, const adgs_sh_grads* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
 	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream) {
+	return adgs_raster_backward_rawsh_opts(P, D, M, R, D_S, background, width, height, means3D, sh, flow_points, semantic, scales, scale_modifier, rotations,
+		viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dpix_depth, dL_dpix_flow,
+		dL_dpix_semantic, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dflow, dL_dsemantic,
+		grad_img_opacity, img_opacity, inv_depth, debug, stream, nullptr);
+}
+
+extern "C" int adgs_raster_backward_rawsh_opts(
+	int P, int D, int M, int R, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+	const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+	const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_flow, const float* dL_dpix_semantic,
+	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
+	float* dL_dcov3D, const adgs_sh_grads* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
+	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream, const adgs_raster_backward_options* options) {
+	float* abs_dst = nullptr;
+	if (read_backward_options(options, "adgs_raster_backward_rawsh_opts", &abs_dst) != 0) return -1;
 	if (!sh || !dL_dsh) { set_error("adgs_raster_backward_rawsh: NULL SH source / gradients"); return -1; }
 	// the gradient block is versioned by its size: what the caller's header did not know yet is absent (NULL)
 	adgs_sh_grads grads_full;
@@ -1350,7 +1415,7 @@ extern "C" int adgs_raster_backward_rawsh(
 	return raster_backward_impl(&src, &dst, P, D, M, R, D_S, background, width, height, means3D, nullptr, nullptr, flow_points, semantic,
 		scales, scale_modifier, rotations, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
 		img_buffer, dL_dpix, dL_dpix_depth, dL_dpix_flow, dL_dpix_semantic, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D,
-		dL_dcov3D, nullptr, dL_dscale, dL_drot, dL_dflow, dL_dsemantic, grad_img_opacity, img_opacity, inv_depth, debug, stream);
+		dL_dcov3D, nullptr, dL_dscale, dL_drot, dL_dflow, dL_dsemantic, grad_img_opacity, img_opacity, inv_depth, debug, stream, abs_dst);
 }
 
 extern "C" int adgs_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present, void* stream_) {
@@ -1442,7 +1507,8 @@ extern "C" long long adgs_test_v2_scanned_candidates(const char* img_buffer, int
 	return sum_tile_words(v.img.tile_scanned, v.wtiles, (hipStream_t)stream_);
 }
 // sizeof of the structs that cross the ABI by pointer: lets a binding check its mirror (which: 0 adgs_sh_source, 1 adgs_sh_grads,
-// 2 adgs_frame_stats, 3 adgs_frame_status, 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam, 7 adgs_raster_options)
+// 2 adgs_frame_stats, 3 adgs_frame_status, 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam, 7 adgs_raster_options, 8 adgs_adam_rows,
+// 9 adgs_raster_backward_options)
 extern "C" unsigned long long adgs_test_env_reads(void) { return g_env_reads.load(); }
 extern "C" size_t adgs_test_abi_sizeof(int which) {
 	switch (which) {
@@ -1455,6 +1521,7 @@ extern "C" size_t adgs_test_abi_sizeof(int which) {
 	case 6: return sizeof(adgs_sh_adam);
 	case 7: return sizeof(adgs_raster_options);
 	case 8: return sizeof(adgs_adam_rows);
+	case 9: return sizeof(adgs_raster_backward_options);
 	default: return 0;
 	}
 }

@@ -91,6 +91,9 @@ struct PreprocessBwdArgs {
 	float* gacc; const Splat* splats; int W, H;
 	ShSource sh_src; ShGradDst sh_dst;   // raw-SH path: gradients go straight to the raw tensors' layout
 	float* out_mean2D; float* out_conic; float* out_opacity; float* out_color; float* out_depth; float* out_flow; float* out_sem;
+	// v2, optional ([P,3], nullptr: not asked): the absolute counterpart of out_mean2D from words 14 / 15 of the line (RenderV2BwdArgs::absgrad) --
+	// (op W/2 sum |L (A dx + B dy)|, op H/2 sum |L (B dx + C dy)|, 0) with the opacity of the Splat line, zero rows for culled Gaussians
+	float* out_mean2D_abs;
 	int D_S;
 	int sh_staging;                  // 0: ADGS_NO_SH_STAGING was set when the FORWARD of this frame ran (api.hip: FrameCfg)
 	const float* ddir;               // [9][P] written by this frame's preprocess forward (PreprocessArgs.ddir) or nullptr: read the `rest` rows again
@@ -110,7 +113,7 @@ constexpr int CHUNK_PREV = WAVE, CHUNK_COUNT = WAVE + 1;      // independent vec
 // every load of every wave queues behind them (the kernel took 375 us whatever its arithmetic, occupancy or locality were changed to).
 constexpr int POOL_BLOCK = 4;
 constexpr int GACC_STRIDE = 16;         // one 64-byte line of gradient accumulators per Gaussian
-constexpr int GACC_USED = 14;           // S0 Sx Sy Sxx Sxy Syy c0 c1 c2 d f0 f1 f2 s0
+constexpr int GACC_USED = 14;           // S0 Sx Sy Sxx Sxy Syy c0 c1 c2 d f0 f1 f2 s0 (words 14, 15: the absolute-gradient sums when asked for, else 0)
 
 // ---- bucket binning (binning.hip) ----
 constexpr int MAX_CELLS = 1024;         // coarse cells one cell_scan workgroup (and one LDS histogram) handles
@@ -195,6 +198,9 @@ struct RenderV2BwdArgs {
 	const float* bg_image; float* dL_dbg_image;      // per-pixel background of the forward and its gradient T_final * dL/dC ([3,H,W], every pixel written)
 	const float* dL_dpix; const float* dL_dpix_depth; const float* dL_dpix_flow; const float* dL_dpix_sem; const float* dL_dpix_opacity;
 	bool do_color, do_flow, do_sem, do_depth, do_opacity;
+	// absolute-gradient statistics (AbsGS): slots 14 / 15 of the line also receive sum |L (A dx + B dy)| and sum |L (B dx + C dy)| over the
+	// replayed (pixel, entry) pairs -- a kernel instantiation of its own; not with sem_src / sem_dst (the main pass only)
+	bool absgrad;
 	float* gacc;                     // [P][GACC_STRIDE], zero-initialised
 	const uint32_t* tile_order;      // workgroup -> tile, longest lists first (launch_tile_order); nullptr: identity
 	uint32_t* tl_start; uint32_t* tl_end;      // -DADGS_TIMELINE experiment build: per-tile wave start / end (100 MHz ticks); else unused

@@ -129,6 +129,7 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 		// v2: every output row is written here, so the caller does not have to zero-fill them
 		if (a.gacc) {
 			a.out_mean2D[3 * (size_t)idx] = 0.f; a.out_mean2D[3 * (size_t)idx + 1] = 0.f; a.out_mean2D[3 * (size_t)idx + 2] = 0.f;
+			if (a.out_mean2D_abs) { a.out_mean2D_abs[3 * (size_t)idx] = 0.f; a.out_mean2D_abs[3 * (size_t)idx + 1] = 0.f; a.out_mean2D_abs[3 * (size_t)idx + 2] = 0.f; }
 			// out_conic / out_color / out_depth / dL_dcov3D are intermediates of the reference's ABI: NULL = not wanted
 			if (a.out_conic) *reinterpret_cast<float4*>(a.out_conic + 4 * (size_t)idx) = make_float4(0.f, 0.f, 0.f, 0.f);
 			if (!rs) a.out_opacity[idx] = 0.f;
@@ -191,6 +192,12 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 		dcon_x = -0.5f * op * u0.w; dcon_y = -0.5f * op * u1.x; dcon_z = -0.5f * op * u1.y;
 		gcol[0] = u1.z; gcol[1] = u1.w; gcol[2] = u2.x; gd = u2.y;
 		st_stream(a.out_mean2D + 3 * (size_t)idx, g2x); st_stream(a.out_mean2D + 3 * (size_t)idx + 1, g2y); st_stream(a.out_mean2D + 3 * (size_t)idx + 2, 0.f);
+		if (a.out_mean2D_abs) {
+			// u3.z, u3.w: sum |L (A dx + B dy)|, sum |L (B dx + C dy)| (render_v2.hip, ABS); the opacity is positive, |op x| = op |x|: the same
+			// (with anti-aliasing: filtered) opacity as the signed terms above, applied once per Gaussian
+			st_stream(a.out_mean2D_abs + 3 * (size_t)idx, op * (float)(0.5 * a.W) * u3.z); st_stream(a.out_mean2D_abs + 3 * (size_t)idx + 1, op * (float)(0.5 * a.H) * u3.w);
+			st_stream(a.out_mean2D_abs + 3 * (size_t)idx + 2, 0.f);
+		}
 		if (a.out_conic) *reinterpret_cast<float4*>(a.out_conic + 4 * (size_t)idx) = make_float4(dcon_x, dcon_y, 0.f, dcon_z);
 		if (AA) { aa_g = u0.x; aa_op = op; }      // the opacity gradient is written below, through the filter factor
 		else if (rs) st_stream(a.sh_dst.scene_opacity + idx, u0.x * act.op * (1.f - act.op));      // d sigmoid
@@ -495,6 +502,7 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream) {
 		          "(the frame's forward ran with ADGS_NO_SH_STAGING, or M != 16)");
 		return -1;
 	}
+	if (a.out_mean2D_abs && !a.gacc) { set_error("preprocess backward: the absolute mean2D gradient needs the default (v2) pipeline's accumulator lines"); return -1; }
 	if (a.antialias && (!a.out_opacity || (!a.gacc && !a.splats))) { set_error("preprocess backward: the anti-aliased frame's opacity gradient has no destination"); return -1; }
 	if (staged) {
 		const size_t lds = (size_t)BW_THREADS * (raw ? SH_ROW_REST : SH_ROW_FULL_LDS) * sizeof(float);

@@ -472,21 +472,26 @@ __global__ void __launch_bounds__(WAVE) render_fwd_v2_kernel(RenderV2FwdArgs a) 
 // ds_read_b128 group (four rows x four quarters) would hit the same four bank quads, so the i-th read of a lane starts at word
 // (i + row) & 3 of its quarter: the four rows of a group (0,3,5,6 / 1,2,4,7 / 8,11,13,10 / 9,10,12,11 -- lanes 56..63 re-read rows
 // 10 and 11, nobody uses their sums) differ mod 4.  The LDS operations of one wave execute in order: no barrier.
-constexpr int RED_ROWS = 14, RED_STRIDE = WAVE;      // floats per value row
+// ABS (the absolute-gradient instantiations, below): SIXTEEN rows -- the two extra sums fill the accumulator line's last two words, lanes
+// 56..63 read rows 14 and 15 (groups 8,11,13,14 / 9,10,12,15: still different mod 4) and every quad's sum is used.
+constexpr int RED_ROWS = 14, RED_ROWS_ABS = 16, RED_STRIDE = WAVE;      // floats per value row
 struct RedAddr { const float4* r[4]; };
+template <int ROWS>
 __device__ __forceinline__ RedAddr red_addresses(const float* s_red, int lane) {
-	const int row = (lane >> 2) < RED_ROWS ? (lane >> 2) : (lane >> 2) - 4;
+	const int row = (lane >> 2) < ROWS ? (lane >> 2) : (lane >> 2) - 4;
 	RedAddr ra;
 #pragma unroll
 	for (int i = 0; i < 4; i++) ra.r[i] = reinterpret_cast<const float4*>(s_red + row * RED_STRIDE + (lane & 3) * 16 + 4 * ((i + row) & 3));
 	return ra;
 }
+template <bool ABS>
 __device__ __forceinline__ float wave_sum14_lds(float* s_red, const RedAddr& ra, int lane, float x0, float x1, float x2, float x3, float x4, float x5, float x6,
-	float x7, float x8, float x9, float x10, float x11, float x12, float x13) {
+	float x7, float x8, float x9, float x10, float x11, float x12, float x13, float x14, float x15) {
 	float* w = s_red + lane;
 	w[0 * RED_STRIDE] = x0; w[1 * RED_STRIDE] = x1; w[2 * RED_STRIDE] = x2; w[3 * RED_STRIDE] = x3; w[4 * RED_STRIDE] = x4;
 	w[5 * RED_STRIDE] = x5; w[6 * RED_STRIDE] = x6; w[7 * RED_STRIDE] = x7; w[8 * RED_STRIDE] = x8; w[9 * RED_STRIDE] = x9;
 	w[10 * RED_STRIDE] = x10; w[11 * RED_STRIDE] = x11; w[12 * RED_STRIDE] = x12; w[13 * RED_STRIDE] = x13;
+	if (ABS) { w[14 * RED_STRIDE] = x14; w[15 * RED_STRIDE] = x15; }
 	const float4 a = *ra.r[0], b = *ra.r[1], c = *ra.r[2], d = *ra.r[3];
 	float v = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w));
 	v += ((c.x + c.y) + (c.z + c.w)) + ((d.x + d.y) + (d.z + d.w));
@@ -497,12 +502,16 @@ __device__ __forceinline__ float wave_sum14_lds(float* s_red, const RedAddr& ra,
 }
 
 // One 16x4 strip of one entry in the backward replay (backward.cu:545-644 for the lane's pixel of that strip).
-struct BwdSums { float op, mx, my, ca, cb, cc, c0, c1, c2, d, f0, f1, f2, s; };      // per-Gaussian partial sums of this lane
-struct BwdEntry { float r, g, b, dval, fx, fy, fz, sem, dx; };                       // the entry's payload (wave-uniform) and the lane's dx
+struct BwdSums { float op, mx, my, ca, cb, cc, c0, c1, c2, d, f0, f1, f2, s, ax, ay; };      // per-Gaussian partial sums of this lane (ax, ay: ABS only)
+struct BwdEntry { float r, g, b, dval, fx, fy, fz, sem, dx, adx, bdx, qb, qc; };             // the entry's payload (wave-uniform) and the lane's dx (adx .. qc: ABS only)
 struct BwdPixel { float gC0, gC1, gC2, gD, gF0, gF1, gF2, gS, tfo, tfb; };           // the pixel's upstream gradients
 template <bool INIT>
 __device__ __forceinline__ void bwd_acc(float& s, float a, float b) { s = INIT ? a * b : fmaf(a, b, s); }
-template <bool INIT>
+// ABS: the strip also accumulates |t_x| and |t_y| of its (pixel, entry) pairs up to the per-Gaussian factor (AbsGS; the densification
+// statistic that does not cancel over a large Gaussian's pixels): |L (A dx + B dy)| and |L (B dx + C dy)| with the entry's conic and
+// A dx, B dx formed once per entry.  Unlike every other geometric sum these are NOT linear in the moments S0 .. Syy: two more per-lane
+// sums, 4 vector instructions per strip (two v_fma for the linear forms, two v_fma with |.| source modifiers for the sums).
+template <bool INIT, bool ABS>
 __device__ __forceinline__ void bwd_strip(BwdSums& v, const BwdEntry& e, const BwdPixel& p, float al, float G, float dy, float& T, float& Bsum,
 	bool do_color, bool do_flow, bool do_sem, bool do_depth, bool do_opacity) {
 	const float rinv = __builtin_amdgcn_rcpf(1.f - al);
@@ -533,6 +542,10 @@ __device__ __forceinline__ void bwd_strip(BwdSums& v, const BwdEntry& e, const B
 	const float L = G * dL_dalpha;
 	const float Ly = L * dy;
 	bwd_acc<INIT>(v.op, G, dL_dalpha); bwd_acc<INIT>(v.my, L, dy); bwd_acc<INIT>(v.cc, Ly, dy);
+	if (ABS) {
+		const float aL = fabsf(L);            // |L u| = |L| |u| exactly; a lane the entry does not reach has G = 0: L = 0, it adds exactly 0
+		bwd_acc<INIT>(v.ax, aL, fabsf(fmaf(e.qb, dy, e.adx))); bwd_acc<INIT>(v.ay, aL, fabsf(fmaf(e.qc, dy, e.bdx)));
+	}
 }
 __device__ __forceinline__ void bwd_finish_moments(BwdSums& v, float dx) {
 	v.mx = dx * v.op; v.ca = dx * v.mx; v.cb = dx * v.my;
@@ -559,7 +572,9 @@ __device__ __forceinline__ uint64_t eval_entry_bwd(const EntryGeom& eg, float py
 
 // FULL: colour, depth, opacity, flow and semantic gradients all present (the training configuration) --
 // the channel switches fold at compile time; otherwise they are wave-uniform run-time flags.
-template <int PPL, bool FULL>
+// ABS: RenderV2BwdArgs::absgrad -- slots 14 and 15 of the accumulator line receive sum |L (A dx + B dy)| and sum |L (B dx + C dy)|.  A template
+// parameter: the instantiations without it are the code they were before the option existed (same registers, LDS and instruction stream).
+template <int PPL, bool FULL, bool ABS>
 __global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) {
 	constexpr int ROWS = 4 * PPL;
 	const bool do_color = FULL || a.do_color, do_flow = FULL || a.do_flow, do_sem = FULL || a.do_sem, do_depth = FULL || a.do_depth, do_opacity = FULL || a.do_opacity;
@@ -569,7 +584,9 @@ __global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) 
 	// (PPL = 4: 5120 + 3584 bytes = 18 per CU); the half-tile kernels (88 registers: 20 per CU) keep the dense 7680-byte layout
 	constexpr int BROW = PPL == 4 ? SPLAT_ROW : 4;
 	__shared__ float4 s_splat[WAVE * BROW];
-	__shared__ __attribute__((aligned(16))) float s_red[RED_ROWS * RED_STRIDE];
+	// ABS: 16 value rows, 512 bytes more (PPL = 4: 9216 bytes = 17 per CU, above the 16 the registers allow; half tiles: 8192 = 20 per CU as before)
+	constexpr int RROWS = ABS ? RED_ROWS_ABS : RED_ROWS;
+	__shared__ __attribute__((aligned(16))) float s_red[RROWS * RED_STRIDE];
 	const int lane = threadIdx.x;
 	const uint32_t tile = a.tile_order ? a.tile_order[blockIdx.x] : blockIdx.x;
 	const uint32_t tx = tile % a.gx, ty = tile / a.gx;
@@ -585,8 +602,8 @@ __global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) 
 	float gC0[PPL], gC1[PPL], gC2[PPL], gF0[PPL], gF1[PPL], gF2[PPL], gD[PPL], gS[PPL];
 	int max_contrib = 0, min_contrib = 0x7fffffff;
 	const int slot = lane >> 2;                      // the gacc slot this lane's quad finishes in wave_sum14_lds
-	const RedAddr red = red_addresses(s_red, lane);
-	const bool writer = (lane & 3) == 0 && slot < GACC_USED;
+	const RedAddr red = red_addresses<RROWS>(s_red, lane);
+	const bool writer = (lane & 3) == 0 && slot < (ABS ? GACC_STRIDE : GACC_USED);
 #pragma unroll
 	for (int k = 0; k < PPL; k++) {
 		const uint32_t py = py0 + 4 * k;
@@ -728,28 +745,28 @@ __global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) 
 				// (dL/dmean2D = -op*(ca Sx + cb Sy)*W/2 ..., dL/dconic = -op/2 * S.., dL/dopacity = S0); the
 				// per-Gaussian factors are applied once per Gaussian in the preprocess backward.
 				BwdSums v;
-				const BwdEntry be = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, dx };
+				const BwdEntry be = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, dx, ABS ? q0.z * dx : 0.f, ABS ? q0.w * dx : 0.f, q0.w, q1.x };
 				// The first strip the entry reaches INITIALISES the 14 sums (every lane writes: a lane the entry does not reach computes
 				// with alpha = G = 0, i.e. adds exactly nothing and leaves its T and B as they are); the others accumulate under exec.
 				// (Only strip 0 can initialise: one straight-line path per possible first strip, or a flag carried through the unrolled
 				// loop, leaves hipcc with 10 - 30 register copies per entry at the joins -- more than the 14 zeroing moves it saves.)
 #define ADGS_BWD_PIXEL(k) const BwdPixel bp = { gC0[k], gC1[k], gC2[k], gD[k], gF0[k], gF1[k], gF2[k], gS[k], tfo[k], tfb[k] }
 #define ADGS_BWD_INITK(k) { ADGS_BWD_PIXEL(k); const bool act = __builtin_amdgcn_inverse_ballot_w64(actm[k]); \
-	bwd_strip<true>(v, be, bp, act ? alpha[k] : 0.f, act ? G[k] : 0.f, dy[k], T[k], Bsum[k], do_color, do_flow, do_sem, do_depth, do_opacity); }
+	bwd_strip<true, ABS>(v, be, bp, act ? alpha[k] : 0.f, act ? G[k] : 0.f, dy[k], T[k], Bsum[k], do_color, do_flow, do_sem, do_depth, do_opacity); }
 #define ADGS_BWD_ACCK(k) if (__builtin_amdgcn_inverse_ballot_w64(actm[k])) { ADGS_BWD_PIXEL(k); \
-	bwd_strip<false>(v, be, bp, alpha[k], G[k], dy[k], T[k], Bsum[k], do_color, do_flow, do_sem, do_depth, do_opacity); }
+	bwd_strip<false, ABS>(v, be, bp, alpha[k], G[k], dy[k], T[k], Bsum[k], do_color, do_flow, do_sem, do_depth, do_opacity); }
 				if (actm[0] != 0ull) { ADGS_BWD_INITK(0) }
-				else v.op = v.my = v.cc = v.c0 = v.c1 = v.c2 = v.d = v.f0 = v.f1 = v.f2 = v.s = 0.f;
+				else v.op = v.my = v.cc = v.c0 = v.c1 = v.c2 = v.d = v.f0 = v.f1 = v.f2 = v.s = v.ax = v.ay = 0.f;
 #pragma unroll
 				for (int k = 1; k < PPL; k++) { ADGS_BWD_ACCK(k) }
 				bwd_finish_moments(v, dx);
 #undef ADGS_BWD_PIXEL
 #undef ADGS_BWD_INITK
 #undef ADGS_BWD_ACCK
-				// 14 wave sums through LDS (slot k of the 64-byte gradient line ends up in the quad of lanes 4k .. 4k+3) -> one atomic
+				// 14 (ABS: 16) wave sums through LDS (slot k of the 64-byte gradient line ends up in the quad of lanes 4k .. 4k+3) -> one atomic
 				// instruction on one 64-byte line.  Absent channels stay exactly 0.
 				PT(t_r0);
-				const float out = wave_sum14_lds(s_red, red, lane, v.op, v.mx, v.my, v.ca, v.cb, v.cc, v.c0, v.c1, v.c2, v.d, v.f0, v.f1, v.f2, v.s);
+				const float out = wave_sum14_lds<ABS>(s_red, red, lane, v.op, v.mx, v.my, v.ca, v.cb, v.cc, v.c0, v.c1, v.c2, v.d, v.f0, v.f1, v.f2, v.s, v.ax, v.ay);
 				if (!FULL && a.sem_dst) {
 					if (writer && (slot < 6 || slot == GACC_USED - 1)) atomicAdd(slot == GACC_USED - 1 ? a.sem_dst + (size_t)gid * a.sem_stride : a.gacc + (size_t)gid * GACC_STRIDE + slot, out);
 				} else if (writer) atomicAdd(a.gacc + (size_t)gid * GACC_STRIDE + slot, out);
@@ -915,19 +932,28 @@ int launch_render_sem_fwd_v2(const RenderV2SemFwdArgs& a, hipStream_t stream) {
 	return 0;
 }
 
+namespace {
+template <bool ABS>
+void launch_render_bwd_v2_t(const RenderV2BwdArgs& a, uint32_t T, bool full, hipStream_t stream) {
+	if (a.ppl == 1) {
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<1, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<1, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+	} else if (a.ppl == 2) {
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<2, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<2, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+	} else {
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<4, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<4, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+	}
+}
+} // namespace
 int launch_render_bwd_v2(const RenderV2BwdArgs& a, hipStream_t stream) {
 	const uint32_t T = (uint32_t)a.gx * a.gy;
 	const bool full = a.do_color && a.do_flow && a.do_sem && a.do_depth && a.do_opacity && a.dL_dpix_opacity != nullptr && !a.sem_src && !a.sem_dst;
-	if (a.ppl == 1) {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<1, true>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<1, false>), dim3(T), dim3(WAVE), 0, stream, a);
-	} else if (a.ppl == 2) {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<2, true>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<2, false>), dim3(T), dim3(WAVE), 0, stream, a);
-	} else {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<4, true>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<4, false>), dim3(T), dim3(WAVE), 0, stream, a);
-	}
+	// the absolute sums of a pair are not the sum of the absolutes of its per-channel shares: no extra semantic replay may carry them
+	if (a.absgrad && (a.sem_src || a.sem_dst)) { set_error("blend backward: absolute gradient sums cannot be formed by the extra semantic channel replays"); return -1; }
+	if (a.absgrad) launch_render_bwd_v2_t<true>(a, T, full, stream);
+	else launch_render_bwd_v2_t<false>(a, T, full, stream);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

@@ -134,7 +134,10 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_flow,
                                  dL_dout_semantic, semantic, flow_points, sh, degree, campos, geomBuffer, R, binningBuffer,
-                                 imageBuffer, img_opacity, grad_img_opacity, inv_depth, debug, plan=None):
+                                 imageBuffer, img_opacity, grad_img_opacity, inv_depth, debug, plan=None, absgrad=False):
+    """absgrad (extension): also compute the ABSOLUTE screen-space gradient sums (include/adgs_rasterizer.h: adgs_raster_backward_options,
+    dL_dmean2D_abs) -- the result then carries one more entry, a [P,3] tensor.  The native call refuses what it cannot serve (a forward of
+    the classic pipeline, more than one semantic channel with a semantic gradient) before its first launch."""
     lib = _lib.lib()
     dev = means3D.device
     P = means3D.size(0)
@@ -159,6 +162,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_ddepths, dL_dconic = (None, None) if lazy else (z(True, P, 1), z(True, P, 2, 2))
     dL_dscales, dL_drotations = z(has_sr, P, 3), z(has_sr, P, 4)
     dL_dflow_points, dL_dsemantic = z(has_flow, P, FLOW_CHANNELS), z(has_sem, P, D_S)
+    dL_dmeans2D_abs = (torch.empty if P != 0 else torch.zeros)((P, 3), dtype=torch.float32, device=dev) if absgrad else None      # every row written
     if P != 0:
         keep = [_prep(t, dev, n) for t, n in (
             (dL_dout_color, "dL_dout_color"), (dL_dout_depth, "dL_dout_depth"), (dL_dout_flow, "dL_dout_flow"), (dL_dout_semantic, "dL_dout_semantic"),
@@ -174,16 +178,20 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             p_bg, p_m3, p_sh, p_col, p_fl, p_sem, p_sc, p_rot, p_cov, p_view, p_proj, p_cam = (_ptr(t) for t in keep2)
         radii_ = _prep(radii, dev, "radii", torch.int32)
         with _on(dev):
-            _lib.check(lib.adgs_raster_backward(
+            native, tail, what = lib.adgs_raster_backward, (), "adgs_raster_backward"
+            if absgrad:
+                bopts = _lib.raster_backward_options(_ptr(dL_dmeans2D_abs))
+                native, tail, what = lib.adgs_raster_backward_opts, (ctypes.byref(bopts),), "adgs_raster_backward_opts"
+            _lib.check(native(
                 P, int(degree), M, int(R), D_S, p_bg, W, H, p_m3, p_sh, p_col, p_fl, p_sem,
                 p_sc, float(scale_modifier), p_rot, p_cov, p_view, p_proj, p_cam,
                 float(tan_fovx), float(tan_fovy), _ptr(radii_), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                 _ptr(gc_), _ptr(gd_), _ptr(gf_), _ptr(gs_),
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_ddepths), _ptr(dL_dmeans3D),
                 _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations), _ptr(dL_dflow_points), _ptr(dL_dsemantic),
-                _ptr(go_), _ptr(io_), int(bool(inv_depth)), int(bool(debug)), _stream_ptr(dev)), "adgs_raster_backward")
+                _ptr(go_), _ptr(io_), int(bool(inv_depth)), int(bool(debug)), _stream_ptr(dev), *tail), what)
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-            dL_dflow_points, dL_dsemantic)
+            dL_dflow_points, dL_dsemantic) + ((dL_dmeans2D_abs,) if absgrad else ())
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
@@ -307,8 +315,10 @@ def rasterize_gaussians_rawsh(background, means3D, opacity, scales, rotations, s
 def rasterize_gaussians_backward_rawsh(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                        dL_dout_color, dL_dout_depth, dL_dout_flow, dL_dout_semantic, semantic, flow_points, sh_raw,
                                        sh_needs_grad, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, img_opacity, grad_img_opacity,
-                                       inv_depth, debug, want_rgb_factor=False, geo_grad_alloc=None, adam=None, plan=None, want_sem_grad=True):
-    """With want_rgb_factor the result carries one more entry: the [P,3] clamp-masked colour gradient every SH gradient row is a
+                                       inv_depth, debug, want_rgb_factor=False, geo_grad_alloc=None, adam=None, plan=None, want_sem_grad=True,
+                                       absgrad=False):
+    """absgrad: as in rasterize_gaussians_backward -- one more entry at the END of the result, the [P,3] absolute gradient sums.
+    With want_rgb_factor the result carries one more entry: the [P,3] clamp-masked colour gradient every SH gradient row is a
     multiple of (include/adgs_exchange.h); combined with sh_needs_grad all False the SH rows are not materialised at all.
     adam: an adgs.optim.BackwardClaim (FusedAdam(in_backward=True)) -- the tensors it names take the Adam step inside the backward
     kernels and get no gradient tensor (include/adgs_optim.h: adgs_sh_adam)."""
@@ -345,6 +355,7 @@ def rasterize_gaussians_backward_rawsh(background, means3D, radii, scales, rotat
             raise RuntimeError("rgb_factor destination must be a contiguous float32 [P,3] tensor on the rasterizer's device")
     else:
         rgb_factor = (e(P, 3) if P != 0 else torch.zeros((0, 3), dtype=torch.float32, device=dev)) if want_rgb_factor else None
+    dL_dmeans2D_abs = (torch.empty if P != 0 else torch.zeros)((P, 3), dtype=torch.float32, device=dev) if absgrad else None
     geo_grads = None
     bg_grad = None
     if P == 0 and len(sh_raw) > 8 and sh_raw[8] is not None:
@@ -385,15 +396,19 @@ def rasterize_gaussians_backward_rawsh(background, means3D, radii, scales, rotat
             p_bg, p_m3, p_fl, p_sem, p_sc, p_rot, p_view, p_proj, p_cam = (_ptr(t) for t in keep2)
         radii_ = _prep(radii, dev, "radii", torch.int32)
         with _on(dev):
-            _lib.check(lib.adgs_raster_backward_rawsh(
+            native, tail, what = lib.adgs_raster_backward_rawsh, (), "adgs_raster_backward_rawsh"
+            if absgrad:
+                bopts = _lib.raster_backward_options(_ptr(dL_dmeans2D_abs))
+                native, tail, what = lib.adgs_raster_backward_rawsh_opts, (ctypes.byref(bopts),), "adgs_raster_backward_rawsh_opts"
+            _lib.check(native(
                 P, int(degree), M, int(R), D_S, p_bg, W, H, p_m3, ctypes.byref(src), p_fl, p_sem, p_sc,
                 float(scale_modifier), p_rot, p_view, p_proj, p_cam, float(tan_fovx), float(tan_fovy), _ptr(radii_),
                 _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(gc_), _ptr(gd_), _ptr(gf_), _ptr(gs_),
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_ddepths), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
                 ctypes.byref(gs), _ptr(dL_dscales), _ptr(dL_drotations), _ptr(dL_dflow_points), _ptr(dL_dsemantic), _ptr(go_), _ptr(io_),
-                int(bool(inv_depth)), int(bool(debug)), _stream_ptr(dev)), "adgs_raster_backward_rawsh")
+                int(bool(inv_depth)), int(bool(debug)), _stream_ptr(dev), *tail), what)
     sh_grads = [g if nd else None for g, nd in zip(sh_grads, sh_needs_grad)]
     if P == 0 or not (len(sh_raw) > 7 and sh_raw[7] is not None and sh_raw[0].size(0) > 0):
         geo_grads = None
     res = (dL_dmeans2D, dL_dopacity, dL_dmeans3D, sh_grads, dL_dscales, dL_drotations, dL_dflow_points, dL_dsemantic)
-    return res + ((rgb_factor,) if rgb_factor is not None else (None,)) + (geo_grads, bg_grad)
+    return res + ((rgb_factor,) if rgb_factor is not None else (None,)) + (geo_grads, bg_grad) + ((dL_dmeans2D_abs,) if absgrad else ())

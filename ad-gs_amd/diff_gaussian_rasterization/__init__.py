@@ -4,7 +4,7 @@ Same public surface and autograd contract as the reference package
 (submodules/depth-diff-gaussian-rasterization/diff_gaussian_rasterization/__init__.py:21-251):
 
     GaussianRasterizationSettings   13-field NamedTuple            (ref :176-189), + `antialiasing` (14th, default False)
-    GaussianRasterizer(nn.Module)   .forward(...) -> 6-tuple, .markVisible(...)   (ref :191-251)
+    GaussianRasterizer(nn.Module)   .forward(...) -> 6-tuple, .markVisible(...)   (ref :191-251), + `means2D_abs=` (absolute gradient)
     rasterize_gaussians(...)        functional form                 (ref :21-46)
 
 so `gaussian_renderer.render()`, `scene/gaussian_model.py` and `train.py` of the
@@ -62,13 +62,29 @@ def _call_with_dump(fn, args, debug, dump_name, phase):
         raise
 
 
+def _check_means2D_abs(means2D_abs, means3D):
+    """means2D_abs (extension, the original AbsGS code's second screen-space leaf): a [P,3] fp32 tensor that requires grad.  The backward
+    then also forms the ABSOLUTE screen-space gradient sums (include/adgs_rasterizer.h: adgs_raster_backward_options) and returns them as
+    this input's gradient -- they arrive in means2D_abs.grad and accumulate over renders as any .grad does."""
+    if not torch.is_tensor(means2D_abs) or tuple(means2D_abs.shape) != (means3D.shape[0], 3) or means2D_abs.dtype != torch.float32:
+        raise RuntimeError("means2D_abs must be a float32 tensor of dimensions (num_points, 3)")
+    if means2D_abs.device != means3D.device:
+        raise RuntimeError("means2D_abs must be on the device of means3D")
+    if not means2D_abs.requires_grad:
+        raise RuntimeError("means2D_abs must require grad: the absolute gradient sums are returned as its gradient")
+    if not torch.is_grad_enabled():
+        raise RuntimeError("means2D_abs was given with gradients switched off: no backward can deliver the absolute gradient sums")
+
+
 class _RasterizeGaussians(torch.autograd.Function):
-    """11 inputs -> 6 outputs; backward returns 11 grads in input order (ref :48-174)."""
+    """11 inputs -> 6 outputs; backward returns 11 grads in input order (ref :48-174).  With a 12th input, means2D_abs, a 12th gradient:
+    the absolute screen-space gradient sums (_check_means2D_abs)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                flow_points, semantic, raster_settings):
+                flow_points, semantic, raster_settings, means2D_abs=None):
         s = raster_settings
+        ctx.absgrad = means2D_abs is not None
         native_args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                        s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, flow_points,
                        semantic, s.sh_degree, s.campos, s.prefiltered, s.inv_depth, s.debug)
@@ -94,11 +110,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                        s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_depth, grad_img_flow,
                        grad_img_semantic, semantic, flow_points, sh, s.sh_degree, s.campos, geom_buf, ctx.num_rendered,
                        binning_buf, img_buf, img_opacity, grad_img_opacity, s.inv_depth, s.debug)
+        kw = dict(absgrad=True) if ctx.absgrad else {}      # (without it: the same native call as ever)
+        res = _call_with_dump(lambda *a: _C.rasterize_gaussians_backward(*a, plan=ctx.plan, **kw), native_args, s.debug, "snapshot_bw.dump", "backward")
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations, grad_flow_points, grad_semantic) = _call_with_dump(
-            lambda *a: _C.rasterize_gaussians_backward(*a, plan=ctx.plan), native_args, s.debug, "snapshot_bw.dump", "backward")
+         grad_rotations, grad_flow_points, grad_semantic) = res[:10]
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, grad_flow_points, grad_semantic, None)
+                grad_cov3Ds_precomp, grad_flow_points, grad_semantic, None) + ((res[10],) if ctx.absgrad else ())
 
 
 class RawSH(NamedTuple):
@@ -133,8 +150,9 @@ class _RasterizeGaussiansRawSH(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, opacities, scales, rotations, flow_points, semantic, scene_dc, obj_dc, scene_rest, obj_rest,
                 scene_deform, obj_deform, func_eval, raster_settings, factor_sink=None, scene_xyz=None, scene_scaling=None, scene_rotation=None,
-                scene_opacity=None, grad_arena=None, bg_image=None, adam=None):
+                scene_opacity=None, grad_arena=None, bg_image=None, adam=None, means2D_abs=None):
         s = raster_settings
+        ctx.absgrad = means2D_abs is not None
         geo = (scene_xyz, scene_scaling, scene_rotation, scene_opacity) if scene_xyz is not None else None
         raw = (scene_dc, obj_dc, scene_rest, obj_rest, scene_deform, obj_deform, func_eval, geo, bg_image)
         plan = {}      # the validated inputs / pointers / adgs_sh_source of this call, for its backward (_C.rasterize_gaussians_rawsh)
@@ -171,16 +189,18 @@ class _RasterizeGaussiansRawSH(torch.autograd.Function):
                 grad_depth, grad_img_flow, grad_img_semantic, semantic, flow_points, raw, need, s.sh_degree, s.campos,
                 geom_buf, ctx.num_rendered, binning_buf, img_buf, img_opacity, grad_img_opacity, s.inv_depth, s.debug,
                 want_rgb_factor=(ctx.factor_sink.next_target(means3D.size(0)) if hasattr(ctx.factor_sink, "next_target") else True) if factored else False,
-                geo_grad_alloc=(arena.take if arena is not None else None), adam=claim, plan=ctx.plan, want_sem_grad=ctx.needs_input_grad[6])
+                geo_grad_alloc=(arena.take if arena is not None else None), adam=claim, plan=ctx.plan, want_sem_grad=ctx.needs_input_grad[6],
+                **(dict(absgrad=True) if ctx.absgrad else {}))
         except Exception:
             if claim is not None:          # the native call validates everything before its first launch: nothing was stepped
                 claim.rollback()
             raise
-        (g_means2D, g_opac, g_means3D, g_sh, g_scales, g_rot, g_flow, g_sem, g_factor, g_geo, g_bg) = res
+        (g_means2D, g_opac, g_means3D, g_sh, g_scales, g_rot, g_flow, g_sem, g_factor, g_geo, g_bg) = res[:11]
         if factored:
             ctx.factor_sink.append(g_factor)
         g_geo = tuple(g_geo) if g_geo is not None else (None,) * 4
-        return (g_means3D, g_means2D, g_opac, g_scales, g_rot, g_flow, g_sem) + tuple(g_sh) + (None, None, None) + g_geo + (None, g_bg, None)
+        return (g_means3D, g_means2D, g_opac, g_scales, g_rot, g_flow, g_sem) + tuple(g_sh) + (None, None, None) + g_geo + (None, g_bg, None) + \
+            ((res[11],) if ctx.absgrad else ())
 
 
 def _no_backward_can_follow(*tensors):
@@ -190,7 +210,11 @@ def _no_backward_can_follow(*tensors):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, flow_points,
-                        semantic, raster_settings):
+                        semantic, raster_settings, means2D_abs=None):
+    if means2D_abs is not None:
+        _check_means2D_abs(means2D_abs, means3D)
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         flow_points, semantic, raster_settings, means2D_abs)
     if _no_backward_can_follow(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, flow_points, semantic):
         # the forward-only render (adgs_raster_render): the same six outputs bit for bit, nothing published for a backward
         s = raster_settings
@@ -214,14 +238,18 @@ class GaussianRasterizer(nn.Module):
             s = self.raster_settings
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
-    def forward_rawsh(self, means3D, means2D, opacities, sh_raw, scales, rotations, flow_points=None, semantic=None, factor_sink=None, bg_image=None):
+    def forward_rawsh(self, means3D, means2D, opacities, sh_raw, scales, rotations, flow_points=None, semantic=None, factor_sink=None, bg_image=None,
+                      means2D_abs=None):
         """Extension (no reference counterpart): like forward(), with the SH coefficients given as a RawSH.
+        means2D_abs: see forward().
         factor_sink: see _RasterizeGaussiansRawSH (factored SH gradients for data-parallel training).
         bg_image [3,H,W]: per-pixel background composited in the blend epilogue -- the first output is then
         `foreground + (1 - img_opacity) * bg_image` (gaussian_renderer/__init__.py:93-94) and bg_image receives a gradient."""
         empty = lambda t: torch.Tensor([]) if t is None else t
         geo4 = [getattr(sh_raw, n, None) for n in ("scene_xyz", "scene_scaling", "scene_rotation", "scene_opacity")]
-        if _no_backward_can_follow(means3D, means2D, opacities, scales, rotations, flow_points, semantic, sh_raw.scene_dc, sh_raw.obj_dc, sh_raw.scene_rest,
+        if means2D_abs is not None:
+            _check_means2D_abs(means2D_abs, means3D)
+        if means2D_abs is None and _no_backward_can_follow(means3D, means2D, opacities, scales, rotations, flow_points, semantic, sh_raw.scene_dc, sh_raw.obj_dc, sh_raw.scene_rest,
                                    sh_raw.obj_rest, sh_raw.scene_deform, sh_raw.obj_deform, bg_image, *geo4):
             s = self.raster_settings
             raw = (sh_raw.scene_dc, sh_raw.obj_dc, sh_raw.scene_rest, sh_raw.obj_rest, sh_raw.scene_deform, sh_raw.obj_deform, sh_raw.func_eval,
@@ -236,10 +264,14 @@ class GaussianRasterizer(nn.Module):
                                               sh_raw.obj_deform, sh_raw.func_eval, self.raster_settings, factor_sink,
                                               getattr(sh_raw, "scene_xyz", None), getattr(sh_raw, "scene_scaling", None),
                                               getattr(sh_raw, "scene_rotation", None), getattr(sh_raw, "scene_opacity", None),
-                                              getattr(sh_raw, "grad_arena", None), bg_image, getattr(sh_raw, "adam", None))
+                                              getattr(sh_raw, "grad_arena", None), bg_image, getattr(sh_raw, "adam", None),
+                                              *(() if means2D_abs is None else (means2D_abs,)))
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, flow_points=None, semantic=None):
+                cov3D_precomp=None, flow_points=None, semantic=None, means2D_abs=None):
+        """means2D_abs (extension, default None = nothing changes): a [P,3] fp32 leaf that requires grad; the backward then also computes the
+        absolute screen-space gradient sums ("AbsGS": sum |term| instead of |sum term| over a Gaussian's pixels) and delivers them in
+        means2D_abs.grad, a drop-in for means2D.grad in the densification statistics."""
         # validation identical to ref :214-218 (neither shs nor colours is allowed)
         if shs is not None and colors_precomp is not None:
             raise Exception('Cannot provice both shs and colors_precomp')
@@ -251,4 +283,4 @@ class GaussianRasterizer(nn.Module):
         empty = lambda t: torch.Tensor([]) if t is None else t
         return rasterize_gaussians(means3D, means2D, empty(shs), empty(colors_precomp), opacities, empty(scales),
                                    empty(rotations), empty(cov3D_precomp), empty(flow_points), empty(semantic),
-                                   self.raster_settings)
+                                   self.raster_settings, **({} if means2D_abs is None else dict(means2D_abs=means2D_abs)))

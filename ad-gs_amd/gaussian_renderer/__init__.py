@@ -66,20 +66,22 @@ def _deformed_state(pc, t, flow_pkg, full_rows=False):
     return pc.get_deformed_pkg(t, **kw), pc.get_deformed_xyz(flow_t)
 
 
-def _rasterize(rasterizer, pc, pkg, means2D, override_color, flow_points, semantic, sh_factor_sink=None, bg_image=None):
-    """bg_image: the environment-map background; on the raw-SH path it is composited in the blend epilogue (the first output is then the
+def _rasterize(rasterizer, pc, pkg, means2D, override_color, flow_points, semantic, sh_factor_sink=None, bg_image=None, means2D_abs=None):
+    """means2D_abs: the second screen-space leaf of pipe.absgrad (None: not asked, the calls below are then the ones they always were).
+    bg_image: the environment-map background; on the raw-SH path it is composited in the blend epilogue (the first output is then the
     final `render`), otherwise the caller composites."""
     scales = pkg["scales"] if "scales" in pkg else pc.get_scaling
     shs = None if override_color is not None else pkg["shs"]
+    kw = {} if means2D_abs is None else dict(means2D_abs=means2D_abs)
     if shs is not None and not torch.is_tensor(shs):
         # a RawSH: the rasterizer reads dc / rest / deformation rows in place, the [N,16,3] tensor is never built
         return rasterizer.forward_rawsh(pkg["xyz"], means2D, pkg["opacity"], shs, scales, pkg["rotation"], flow_points=flow_points,
                                         semantic=semantic, factor_sink=None if sh_factor_sink is None else sh_factor_sink(pkg["xyz"]),
-                                        bg_image=bg_image), bg_image is not None
+                                        bg_image=bg_image, **kw), bg_image is not None
     if sh_factor_sink is not None:
         raise RuntimeError("sh_factor_sink needs the raw-SH path (a model whose get_deformed_pkg hands out a RawSH)")
     return rasterizer(means3D=pkg["xyz"], means2D=means2D, opacities=pkg["opacity"], shs=shs, colors_precomp=override_color, scales=scales,
-                      rotations=pkg["rotation"], flow_points=flow_points, semantic=semantic), False
+                      rotations=pkg["rotation"], flow_points=flow_points, semantic=semantic, **kw), False
 
 
 class _LazyResult(dict):
@@ -127,11 +129,16 @@ def screenspace_points(n, device):
 def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_color=None, flow_pkg=None, render_objmask=False,
            sh_factor_sink=None):
     """sh_factor_sink (extension, default off): adgs.dp.FactoredSHExchange.sink_for -- data-parallel training exchanges the SH
-    gradients in factored form; the backward of this render then leaves them to FactoredSHExchange.reduce()."""
+    gradients in factored form; the backward of this render then leaves them to FactoredSHExchange.reduce().
+    pipe.absgrad (extension, read with getattr, default off): the result also carries 'viewspace_points_abs', a second leaf like
+    'viewspace_points' whose .grad receives the ABSOLUTE screen-space gradient sums (AbsGS / gsplat's absgrad: sum |term| over a
+    Gaussian's pixels instead of |sum term|); adgs.model's add_densification_stats then accumulates that statistic instead of the
+    signed one (raise densify_grad_threshold with it, typically about fourfold).  Under torch.no_grad() the key is absent."""
     n_pts = pc.get_pts_num if hasattr(pc, "get_pts_num") else pc.get_xyz.shape[0]
     device = (pc._scene_xyz if hasattr(pc, "_scene_xyz") else pc.get_xyz).device
     # the densification statistics read the gradient of the screen-space means from this tensor (.grad[:, :2])
     means2D = screenspace_points(n_pts, device)
+    means2D_abs = screenspace_points(n_pts, device) if (bool(getattr(pipe, "absgrad", False)) and torch.is_grad_enabled()) else None
 
     rasterizer = GaussianRasterizer(raster_settings=_camera_settings(viewpoint_camera, pc, pipe, scaling_modifier, device))
     pkg, flow_points = _deformed_state(pc, viewpoint_camera.time, flow_pkg, full_rows=override_color is not None)
@@ -140,7 +147,7 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
     # gaussian_renderer/__init__.py:93-94) and the blend backward returns dL/dbackground = T * dL/drender -- no element-wise pass
     background = env_map.get_image_background(viewpoint_camera) if env_map is not None else None
     (first, radii, depth, img_opacity, img_flow, img_semantic), composited = _rasterize(rasterizer, pc, pkg, means2D, override_color, flow_points,
-                                                                                         semantic, sh_factor_sink, bg_image=background)
+                                                                                         semantic, sh_factor_sink, bg_image=background, means2D_abs=means2D_abs)
     if composited:
         rendered, foreground = first, None                      # 'foreground' on demand: render - (1 - O) * background
     else:
@@ -167,6 +174,8 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
                depth=depth.squeeze(0), img_opacity=img_opacity.squeeze(0),
                background=background, img_flow=img_flow if flow_points is not None else None,
                img_semantic=img_semantic if semantic is not None else None)
+    if means2D_abs is not None:
+        out["viewspace_points_abs"] = means2D_abs
     if foreground is not None:
         out["foreground"] = foreground
     else:                                                       # composited in the epilogue: the reference's 'foreground' entry on first access

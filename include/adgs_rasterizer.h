@@ -290,6 +290,43 @@ int adgs_raster_render_rawsh_opts(
 	const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
 	float* out_color, float* out_depth, float* img_opacity, float* img_flow, float* img_semantic,
 	int inv_depth, int* radii, int debug, void* stream, const adgs_raster_options* options);
+/* Options of a backward (the `_opts` backward entries below); versioned by its size exactly like adgs_raster_options (struct_bytes =
+ * sizeof of the caller's header, growth at the end only, NULL = the defaults: every member 0 / NULL). */
+typedef struct adgs_raster_backward_options {
+	uint64_t struct_bytes;
+	/* [P,3] or NULL (not asked): the ABSOLUTE screen-space gradient ("AbsGS", gsplat's absgrad).  dL_dmean2D[g] is a sum over the
+	 * (pixel, Gaussian) pairs the backward replays, dL_dmean2D[g].x = sum t_x(pair) with t_x = dL/dG * dG/d(delta x) * W/2 (y: H/2), and
+	 * the terms of a large Gaussian's pixels cancel.  This output is sum |t_x(pair)|, sum |t_y(pair)|, 0 -- the same terms, the same
+	 * conventions (gates of the forward, gradient through the 0.99 alpha cap, the opacity-T quirk), every row written, rows of culled
+	 * Gaussians (radii == 0) zero: a drop-in for dL_dmean2D in adgs_densification_stats.  It exists only inside the blend backward, which
+	 * runs a kernel instantiation of its own for it (two more sums per pair; cost: EXPERIMENTS.md); NULL costs nothing.
+	 * Refused (error, nothing launched): a frame whose forward ran the classic pipeline; D_S > 1 with a semantic gradient (the extra
+	 * channels are replayed by separate passes, and a sum of per-pass absolutes is not the absolute of the pair's term). */
+	float* dL_dmean2D_abs;
+} adgs_raster_backward_options;
+
+/* adgs_raster_backward / adgs_raster_backward_rawsh with options: the same arguments and a trailing `options` (NULL = the defaults; the
+ * two entries above are these with NULL). */
+int adgs_raster_backward_opts(
+	int P, int D, int M, int R, int D_S, const float* background, int width, int height,
+	const float* means3D, const float* shs, const float* colors_precomp, const float* flow_points, const float* semantic,
+	const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+	const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+	const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+	const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_flow, const float* dL_dpix_semantic,
+	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
+	float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
+	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream, const adgs_raster_backward_options* options);
+int adgs_raster_backward_rawsh_opts(
+	int P, int D, int M, int R, int D_S, const float* background, int width, int height,
+	const float* means3D, const adgs_sh_source* sh, const float* flow_points, const float* semantic,
+	const float* scales, float scale_modifier, const float* rotations,
+	const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+	const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+	const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_flow, const float* dL_dpix_semantic,
+	float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
+	float* dL_dcov3D, const adgs_sh_grads* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dflow, float* dL_dsemantic,
+	const float* grad_img_opacity, const float* img_opacity, int inv_depth, int debug, void* stream, const adgs_raster_backward_options* options);
 /* ... and for the backward of a given forward (its state buffers, shape and point count): what THAT forward's pipeline needs, from the
  * library's frame table -- the backward never consults the environment.  Unknown state: 1 (zero-fill is always safe). */
 int adgs_raster_backward_needs_zero_init(const char* geom_buffer, const char* img_buffer, int width, int height, int P);
