@@ -119,6 +119,11 @@ SIGNATURES = {
     # include/adgs_knn_points.h
     "adgs_knn_points_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "adgs_knn_points": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    # include/adgs_bilagrid.h
+    "adgs_bilagrid_slice_forward": (c_i, [c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "adgs_bilagrid_slice_backward": (c_i, [c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_bilagrid_tv_forward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "adgs_bilagrid_tv_backward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
@@ -134,6 +139,7 @@ SIGNATURES = {
     "adgs_test_sort_temp_bytes": (ctypes.c_size_t, [ctypes.c_size_t]),
     "adgs_test_sort_pairs_u64": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
     "adgs_test_sort_pairs_u32": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
+    "adgs_test_bilagrid_path": (c_i, [c_i, c_i, c_i, c_i, c_i]),
 }
 
 

@@ -47,6 +47,11 @@ void adgs_test_set_capacity_hints(long long pairs, long long fine_pairs);      /
  * per-cell lists.  Returns 0, -1 when no bucket-binned frame has created the table yet. */
 int adgs_test_scramble_slab_bounds(unsigned seed);
 
+/* Which way adgs_bilagrid_slice_forward / _backward (include/adgs_bilagrid.h) run a call of this shape -- the choice depends on the shape
+ * alone: 1 = grid columns staged / gradients accumulated in LDS, 0 = the footprint of a pixel tile can exceed the LDS budget (a small image
+ * under a large grid): gathers from and atomics into global memory.  -1: a shape the entry points refuse. */
+int adgs_test_bilagrid_path(int L, int Hg, int Wg, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif
