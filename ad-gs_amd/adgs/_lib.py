@@ -124,6 +124,11 @@ SIGNATURES = {
     "adgs_bilagrid_slice_backward": (c_i, [c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_bilagrid_tv_forward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "adgs_bilagrid_tv_backward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    # include/adgs_filter3d.h
+    "adgs_filter3d_accumulate": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "adgs_filter3d_finalize": (c_i, [c_p, c_i, c_p, c_p, c_p]),
+    "adgs_filter3d_apply_forward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_filter3d_apply_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

@@ -87,7 +87,12 @@ def save_ply(model, path):
     Ns, No = model._scene_xyz.shape[0], model._obj_xyz.shape[0]
     obj = np.concatenate([np.zeros((Ns, 1), np.float32), np.ones((No, 1), np.float32)], 0)
     names = construct_list_of_attributes(shs_dc.shape[1], shs_rest.shape[1], scale.shape[1], rotation.shape[1])
-    write_ply(path, names, np.concatenate((xyz, np.zeros_like(xyz), shs_dc, shs_rest, opacities, scale, rotation, obj), axis=1))
+    columns = (xyz, np.zeros_like(xyz), shs_dc, shs_rest, opacities, scale, rotation, obj)
+    filter_3d = getattr(model, "filter_3D", None)
+    if filter_3d is not None:          # Mip-Splatting's extra property, last; a model without a filter writes the file it always wrote
+        names = names + ["filter_3D"]
+        columns += (filter_3d.detach().reshape(-1, 1).cpu().numpy(),)
+    write_ply(path, names, np.concatenate(columns, axis=1))
     torch.save((model.xyz_deform_param, model.rotation_deform_param, model.shs_deform_param_scene, model.shs_deform_param_obj,
                 model.background_deform_param, model.gs_time, model.gs_time_sigma, model.use_time_mask, model.order_args,
                 getattr(model, "scene_extent", 0.0)), os.path.join(os.path.dirname(os.path.abspath(path)), "deform.pth"))
@@ -134,4 +139,7 @@ def load_ply(model, path, device="cuda"):
     model.gs_time = gs_time.to(device)
     model.gs_time_sigma = G(gs_time_sigma)
     model.active_sh_degree = model.max_sh_degree
+    # rows in the model's order: scene, then objects (a file this package wrote is already in that order)
+    model.filter_3D = None if "filter_3D" not in c else torch.tensor(
+        np.concatenate([col("filter_3D")[scene_mask], col("filter_3D")[obj_mask]])[:, None], dtype=torch.float32, device=device)
     return model

@@ -5,12 +5,15 @@ getters (`get_xyz`, `get_scaling`, `get_obj_mask`, `get_deformed_xyz(t)`, `get_d
 (adgs.deform) instead of ~30 small PyTorch kernels.  The training-side methods that sit next to the hot
 path keep their reference names too: training_setup (fused Adam with the reference's group names),
 add_densification_stats, densify_and_prune, reset_opacity, set_obj_near_idx (adgs.densify / adgs.knn: HIP),
-save_ply / load_ply (adgs.io: the reference's point_cloud.ply + deform.pth).
+save_ply / load_ply (adgs.io: the reference's point_cloud.ply + deform.pth).  Opt-in extension: the 3D smoothing filter of
+Mip-Splatting (adgs.filter3d) under the names of its trainer -- filter_3D, compute_3d_filter, get_scaling_with_3D_filter,
+get_opacity_with_3D_filter.
 """
 import torch
 
 from . import deform
 from . import densify as _densify
+from . import filter3d as _filter3d
 from . import io as _io
 from . import knn as _knn
 
@@ -111,6 +114,28 @@ class SyntheticGaussianModel:
     def get_deformed_xyz(self, t):
         return deform.get_deformed_xyz(self, t)
 
+    # ---- the 3D smoothing filter of Mip-Splatting (adgs.filter3d; opt-in: gaussian_renderer.render() reads it under pipe.filter_3d) ----
+    filter_3D = None   # [N, 1] after compute_3d_filter(); densify_and_prune and load_ply of a file without the property reset it to None
+
+    def compute_3d_filter(self, cameras):
+        """filter_3D from the training cameras: before the first iteration, after every densification and every 100 iterations while the
+        positions still move much (adgs.filter3d.compute_3d_filter)."""
+        return _filter3d.compute_3d_filter(self, cameras)
+
+    def _filtered(self, t):
+        if self.filter_3D is None or self.filter_3D.shape[0] != self.get_pts_num:
+            raise RuntimeError("the model has no 3D filter for its %d Gaussians: call compute_3d_filter(cameras) first" % self.get_pts_num)
+        pkg = deform.get_deformed_pkg(self, t, want=("opacity", "scales"))
+        return _filter3d.apply(pkg["scales"], pkg["opacity"], self.filter_3D)
+
+    @property
+    def get_scaling_with_3D_filter(self):
+        return self._filtered(0.0)[0]
+
+    def get_opacity_with_3D_filter(self, t):
+        """The activated opacity at time t (time mask of the object rows included) times the filter's compensation."""
+        return self._filtered(t)[1]
+
     raw_sh = False     # True: get_deformed_pkg leaves the SH coefficients in raw layout (RawSH) for forward_rawsh
     raw_scene = False  # True (with raw_sh): the scene range is not deformed/activated at all -- the rasterizer's preprocess reads the raw
     #                    scene tensors (adgs.deform.get_deformed_pkg(raw_scene=True)); rows [0, Ns) of 'xyz' / 'rotation' / 'opacity' /
@@ -180,6 +205,7 @@ class SyntheticGaussianModel:
 
     def densify_and_prune(self, max_scene_grad, max_obj_grad, min_opacity, prune_big_points):
         info = _densify.densify_and_prune(self, max_scene_grad, max_obj_grad, min_opacity, prune_big_points)
+        self.filter_3D = None          # rows moved, appeared and vanished: compute_3d_filter() again
         self.set_obj_near_idx()
         return info
 

@@ -133,7 +133,11 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
     pipe.absgrad (extension, read with getattr, default off): the result also carries 'viewspace_points_abs', a second leaf like
     'viewspace_points' whose .grad receives the ABSOLUTE screen-space gradient sums (AbsGS / gsplat's absgrad: sum |term| over a
     Gaussian's pixels instead of |sum term|); adgs.model's add_densification_stats then accumulates that statistic instead of the
-    signed one (raise densify_grad_threshold with it, typically about fourfold).  Under torch.no_grad() the key is absent."""
+    signed one (raise densify_grad_threshold with it, typically about fourfold).  Under torch.no_grad() the key is absent.
+    pipe.filter_3d (extension, read with getattr, default off): the 3D smoothing filter of Mip-Splatting -- the rasterizer receives
+    adgs.filter3d.apply(scales, opacity, pc.filter_3D) instead of the deformation pass's scales and opacity (pc.compute_3d_filter(cameras)
+    first, and again after every densification).  The result's 'opacity' / 'scales' entries stay the unfiltered ones, which is what
+    densification and pruning read.  A model on the raw-scene path materialises its scene rows for such a frame."""
     n_pts = pc.get_pts_num if hasattr(pc, "get_pts_num") else pc.get_xyz.shape[0]
     device = (pc._scene_xyz if hasattr(pc, "_scene_xyz") else pc.get_xyz).device
     # the densification statistics read the gradient of the screen-space means from this tensor (.grad[:, :2])
@@ -141,12 +145,23 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
     means2D_abs = screenspace_points(n_pts, device) if (bool(getattr(pipe, "absgrad", False)) and torch.is_grad_enabled()) else None
 
     rasterizer = GaussianRasterizer(raster_settings=_camera_settings(viewpoint_camera, pc, pipe, scaling_modifier, device))
-    pkg, flow_points = _deformed_state(pc, viewpoint_camera.time, flow_pkg, full_rows=override_color is not None)
+    filter_3d = None
+    if bool(getattr(pipe, "filter_3d", False)):
+        filter_3d = getattr(pc, "filter_3D", None)
+        if filter_3d is None or filter_3d.shape[0] != n_pts:
+            raise RuntimeError("pipe.filter_3d is on but the model has %s: call compute_3d_filter(cameras) before rendering and after every densification" % (
+                "no 3D filter" if filter_3d is None else "a 3D filter of %d rows for %d Gaussians" % (filter_3d.shape[0], n_pts)))
+    pkg, flow_points = _deformed_state(pc, viewpoint_camera.time, flow_pkg, full_rows=override_color is not None or filter_3d is not None)
+    raster_pkg = pkg
+    if filter_3d is not None:
+        from adgs import filter3d as _filter3d
+        raster_pkg = dict(pkg)
+        raster_pkg["scales"], raster_pkg["opacity"] = _filter3d.apply(pkg["scales"] if "scales" in pkg else pc.get_scaling, pkg["opacity"], filter_3d)
     semantic = (pc.obj_mask_float if hasattr(pc, "obj_mask_float") else pc.get_obj_mask.float()[..., None]) if render_objmask else None
     # the environment-map background first: on the raw-SH path the blend epilogue composites it (`render = C + T * background`,
     # gaussian_renderer/__init__.py:93-94) and the blend backward returns dL/dbackground = T * dL/drender -- no element-wise pass
     background = env_map.get_image_background(viewpoint_camera) if env_map is not None else None
-    (first, radii, depth, img_opacity, img_flow, img_semantic), composited = _rasterize(rasterizer, pc, pkg, means2D, override_color, flow_points,
+    (first, radii, depth, img_opacity, img_flow, img_semantic), composited = _rasterize(rasterizer, pc, raster_pkg, means2D, override_color, flow_points,
                                                                                          semantic, sh_factor_sink, bg_image=background, means2D_abs=means2D_abs)
     if composited:
         rendered, foreground = first, None                      # 'foreground' on demand: render - (1 - O) * background

@@ -8,7 +8,11 @@
        `near_idx_reset_interval` iterations set_obj_near_idx, every `opacity_reset_interval` iterations reset_opacity (train.py:146-158)
        -> both Adam steps (train.py:163-167).
 
-    python examples/train_iteration.py [--config C3] [--iters 60] [--env-res 8192] [--cameras 16] [--no-adam-in-backward] [--json]
+    python examples/train_iteration.py [--config C3] [--iters 60] [--env-res 8192] [--cameras 16] [--no-adam-in-backward] [--filter-3d] [--json]
+
+--filter-3d (opt-in, default off): the 3D smoothing filter of Mip-Splatting (adgs.filter3d) -- model.compute_3d_filter(cameras) before the
+first iteration, after every densification and every 100 iterations while densification goes on (here: always), and render() under
+pipe.filter_3d.
 
 The Adam step of the SH `rest` and SH deformation tensors (81 of a scene Gaussian's 95 parameters) is applied inside the rasterizer's
 backward (FusedAdam(in_backward=True) + arm_backward(): bit-identical to the separate step, tests/test_gpu_optim.py) in the
@@ -37,6 +41,7 @@ OPT = types.SimpleNamespace(lambda_dssim=0.2, lambda_l1=1.0, lambda_depth=0.1, l
                             lambda_reg=0.5, lambda_sigma_reg=0.5, near_num=8, near_idx_reset_interval=10, densification_interval=200,
                             densify_scene_grad_threshold=None, densify_obj_grad_threshold=None, opacity_reset_interval=3000, min_opacity=0.005, env_lr=1e-2)
 FUSED_IMAGE_LOSSES = os.environ.get("ADGS_FUSED_IMAGE_LOSSES", "1") != "0"
+FILTER_3D_INTERVAL = 100          # Mip-Splatting's trainer recomputes the 3D filter every 100 iterations until densification ends
 STAGES = ("regularisers", "render", "losses", "backward", "densify_stats", "near_idx_or_densify", "adam_gaussians", "adam_env_map")
 
 
@@ -134,6 +139,10 @@ def iteration(it, model, cams, env_map, clock, state):
     from gaussian_renderer import render
     opt = OPT
     pipe = types.SimpleNamespace(inv_depth=True, debug=False)
+    if state.get("filter_3d"):
+        pipe.filter_3d = True
+        if model.filter_3D is None or it % FILTER_3D_INTERVAL == 0:          # None: the first iteration, or a densification dropped it
+            model.compute_3d_filter(cams)
     cam = cams[it % len(cams)]                                               # train.py:55-61
     flow_pkg = cam.flow[0]                                                   # :66-71
     clock.mark("start")
@@ -197,11 +206,11 @@ def iteration(it, model, cams, env_map, clock, state):
     return total.detach()
 
 
-def run(config="C3", iters=60, env_res=8192, cameras=16, warm=12, device=None, stages=True, adam_in_backward=True):
+def run(config="C3", iters=60, env_res=8192, cameras=16, warm=12, device=None, stages=True, adam_in_backward=True, filter_3d=False):
     import torch
     device = device or torch.device("cuda", 0)
     cfg, model, cams, env_map = build(config, env_res, device, cameras, adam_in_backward)
-    state = {}
+    state = {"filter_3d": True} if filter_3d else {}
     off = StageClock(False)
     for i in range(warm):
         iteration(i, model, cams, env_map, off, state)
@@ -223,7 +232,8 @@ def run(config="C3", iters=60, env_res=8192, cameras=16, warm=12, device=None, s
             _ = float(state["ema"])                                          # what the progress bar prints (train.py:133-138)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / iters
-    return {"workload": "%s training iteration: render (deformation, flow, semantic, %d^2 environment map) + L1/SSIM + depth + flow + 2 BCE + 3 regularisers "
+    extra = {"filter_3d": True} if filter_3d else {}
+    return {**extra, "workload": "%s training iteration: render (deformation, flow, semantic, %d^2 environment map) + L1/SSIM + depth + flow + 2 BCE + 3 regularisers "
                         "+ backward + densification statistics + fused Adam (Gaussians, environment map); set_obj_near_idx every %d and "
                         "densify_and_prune every %d iterations; %d cameras" % (config, env_res, OPT.near_idx_reset_interval, OPT.densification_interval, len(cams)),
             "iterations": iters, "adam_in_backward": bool(adam_in_backward), "ms_per_iteration": round(dt * 1e3, 4), "iterations_per_s": round(1.0 / dt, 2),
@@ -239,12 +249,13 @@ def main():
     ap.add_argument("--env-res", type=int, default=8192)
     ap.add_argument("--cameras", type=int, default=16)
     ap.add_argument("--no-adam-in-backward", action="store_true")
+    ap.add_argument("--filter-3d", action="store_true", help="train with the 3D smoothing filter of Mip-Splatting (adgs.filter3d)")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
-    res = run(args.config, args.iters, args.env_res, args.cameras, adam_in_backward=not args.no_adam_in_backward)
+    res = run(args.config, args.iters, args.env_res, args.cameras, adam_in_backward=not args.no_adam_in_backward, filter_3d=args.filter_3d)
     if args.json:
         print(json.dumps(res))
     else:
