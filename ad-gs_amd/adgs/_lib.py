@@ -238,6 +238,13 @@ def check(code, what):
     return code
 
 
+def call(symbol, device, *args):
+    """lib().<symbol>(*args, <current stream of device>) with `device` current: how the operators call every native entry whose last
+    parameter is the stream.  Returns the checked return code; a negative one raises RuntimeError("<symbol> failed: <adgs_last_error>")."""
+    with on_device(device):
+        return check(getattr(lib(), symbol)(*args, stream_ptr(device)), symbol)
+
+
 def frame_stats():
     st = FrameStats()
     lib().adgs_get_frame_stats(ctypes.byref(st))

@@ -52,9 +52,7 @@ class _Slice(torch.autograd.Function):
         L, Hg, Wg = g.shape[2:]
         H, W = img.shape[1:]
         out = torch.empty_like(img)
-        with _lib.on_device(g.device):
-            _lib.check(_lib.lib().adgs_bilagrid_slice_forward(L, Hg, Wg, g[index].data_ptr(), H, W, img.data_ptr(), out.data_ptr(),
-                                                              _lib.stream_ptr(g.device)), "adgs_bilagrid_slice_forward")
+        _lib.call("adgs_bilagrid_slice_forward", g.device, L, Hg, Wg, g[index].data_ptr(), H, W, img.data_ptr(), out.data_ptr())
         ctx.save_for_backward(g, img)
         ctx.index = index
         return out
@@ -67,11 +65,8 @@ class _Slice(torch.autograd.Function):
         go = g_out.contiguous().float()
         d_grids = torch.zeros_like(g) if ctx.needs_input_grad[0] else None          # dense, zero outside `index`
         d_image = torch.empty_like(img) if ctx.needs_input_grad[1] else None
-        with _lib.on_device(g.device):
-            _lib.check(_lib.lib().adgs_bilagrid_slice_backward(L, Hg, Wg, g[ctx.index].data_ptr(), H, W, img.data_ptr(), go.data_ptr(),
-                                                               d_grids[ctx.index].data_ptr() if d_grids is not None else None,
-                                                               d_image.data_ptr() if d_image is not None else None,
-                                                               _lib.stream_ptr(g.device)), "adgs_bilagrid_slice_backward")
+        _lib.call("adgs_bilagrid_slice_backward", g.device, L, Hg, Wg, g[ctx.index].data_ptr(), H, W, img.data_ptr(), go.data_ptr(),
+                  d_grids[ctx.index].data_ptr() if d_grids is not None else None, d_image.data_ptr() if d_image is not None else None)
         return d_grids, d_image, None
 
 
@@ -83,9 +78,7 @@ class _TotalVariation(torch.autograd.Function):
         N, _, L, Hg, Wg = g.shape
         work, tok = _work(g.device, TV_WORK_DOUBLES)
         out = torch.empty(1, dtype=torch.float32, device=g.device)
-        with _lib.on_device(g.device):
-            _lib.check(_lib.lib().adgs_bilagrid_tv_forward(N, L, Hg, Wg, g.data_ptr(), work.data_ptr(), out.data_ptr(), _lib.stream_ptr(g.device)),
-                       "adgs_bilagrid_tv_forward")
+        _lib.call("adgs_bilagrid_tv_forward", g.device, N, L, Hg, Wg, g.data_ptr(), work.data_ptr(), out.data_ptr())
         tok.done()
         ctx.save_for_backward(g)
         return out[0]
@@ -96,9 +89,7 @@ class _TotalVariation(torch.autograd.Function):
         N, _, L, Hg, Wg = g.shape
         gl = g_loss.reshape(1).float().contiguous()
         out = torch.empty_like(g)
-        with _lib.on_device(g.device):
-            _lib.check(_lib.lib().adgs_bilagrid_tv_backward(N, L, Hg, Wg, g.data_ptr(), gl.data_ptr(), out.data_ptr(), _lib.stream_ptr(g.device)),
-                       "adgs_bilagrid_tv_backward")
+        _lib.call("adgs_bilagrid_tv_backward", g.device, N, L, Hg, Wg, g.data_ptr(), gl.data_ptr(), out.data_ptr())
         return out
 
 

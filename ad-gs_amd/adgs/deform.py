@@ -139,10 +139,6 @@ def _make_func_eval_cached(v, order_args, n_params):
     return f
 
 
-def _stream(dev):
-    return _lib.stream_ptr(dev)
-
-
 def _dp(t):
     return None if (t is None or t.numel() == 0) else t.data_ptr()
 
@@ -156,9 +152,7 @@ class _FuncEvalFn(torch.autograd.Function):
         lead, D = p.shape[:-2], p.shape[-2]
         N = int(np.prod(lead)) if len(lead) else 1
         out = torch.empty(*lead, D, dtype=torch.float32, device=p.device)
-        with _lib.on_device(p.device):
-            _lib.check(_lib.lib().adgs_func_eval_forward(N, D, p.data_ptr(), ctypes.byref(feval), out.data_ptr(), _stream(p.device)),
-                       "adgs_func_eval_forward")
+        _lib.call("adgs_func_eval_forward", p.device, N, D, p.data_ptr(), ctypes.byref(feval), out.data_ptr())
         ctx.save_for_backward(p)
         ctx.feval, ctx.N, ctx.D = feval, N, D
         return out
@@ -168,9 +162,7 @@ class _FuncEvalFn(torch.autograd.Function):
         (p,) = ctx.saved_tensors
         gp = torch.zeros_like(p)
         g = g.contiguous().float()
-        with _lib.on_device(p.device):
-            _lib.check(_lib.lib().adgs_func_eval_backward(ctx.N, ctx.D, p.data_ptr(), ctypes.byref(ctx.feval), g.data_ptr(), gp.data_ptr(),
-                                                          _stream(p.device)), "adgs_func_eval_backward")
+        _lib.call("adgs_func_eval_backward", p.device, ctx.N, ctx.D, p.data_ptr(), ctypes.byref(ctx.feval), g.data_ptr(), gp.data_ptr())
         return gp, None
 
 
@@ -228,11 +220,10 @@ class _DeformPkgFn(torch.autograd.Function):
         o = DeformOutputs()
         for k, v in outs.items():
             setattr(o, k, _dp(v))
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().adgs_deform_forward_flow(
-                ctypes.byref(p), ctypes.byref(fe["xyz"]), ctypes.byref(fe["rotation"]), ctypes.byref(fe["shs"]), ctypes.byref(fe["background"]),
-                ctypes.byref(fe["xyz_flow"]) if flow_t is not None else None, ctypes.byref(fe["background_flow"]) if flow_t is not None else None,
-                ctypes.byref(o), _dp(flow_xyz), _stream(dev)), "adgs_deform_forward_flow")
+        _lib.call("adgs_deform_forward_flow", dev,
+                  ctypes.byref(p), ctypes.byref(fe["xyz"]), ctypes.byref(fe["rotation"]), ctypes.byref(fe["shs"]), ctypes.byref(fe["background"]),
+                  ctypes.byref(fe["xyz_flow"]) if flow_t is not None else None, ctypes.byref(fe["background_flow"]) if flow_t is not None else None,
+                  ctypes.byref(o), _dp(flow_xyz))
         ctx.save_for_backward(*[x for x in ts if x is not None])
         ctx.present = [x is not None for x in ts]
         ctx.meta, ctx.fe, ctx.dims = meta, fe, (Ns, No, M)
@@ -293,12 +284,10 @@ class _DeformPkgFn(torch.autograd.Function):
                 grads[n] = g if g is not None else torch.empty_like(src)
             setattr(gs, n, _dp(grads[n]))
         fe = ctx.fe
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().adgs_deform_backward_flow(
-                ctypes.byref(p), ctypes.byref(fe["xyz"]), ctypes.byref(fe["rotation"]), ctypes.byref(fe["shs"]), ctypes.byref(fe["background"]),
-                ctypes.byref(fe["xyz_flow"]) if flow_t is not None else None, ctypes.byref(fe["background_flow"]) if flow_t is not None else None,
-                _dp(up["xyz"]), _dp(up["rotation"]), _dp(up["shs"]), _dp(up["opacity"]), _dp(up["scales"]), _dp(up["flow"]),
-                ctypes.byref(gs), _stream(dev)), "adgs_deform_backward_flow")
+        _lib.call("adgs_deform_backward_flow", dev,
+                  ctypes.byref(p), ctypes.byref(fe["xyz"]), ctypes.byref(fe["rotation"]), ctypes.byref(fe["shs"]), ctypes.byref(fe["background"]),
+                  ctypes.byref(fe["xyz_flow"]) if flow_t is not None else None, ctypes.byref(fe["background_flow"]) if flow_t is not None else None,
+                  _dp(up["xyz"]), _dp(up["rotation"]), _dp(up["shs"]), _dp(up["opacity"]), _dp(up["scales"]), _dp(up["flow"]), ctypes.byref(gs))
         return (None,) + tuple(grads.get(n) for n in _PTRS)
 
 

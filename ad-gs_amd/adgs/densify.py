@@ -34,10 +34,6 @@ class DensifySide(ctypes.Structure):
                 ("big_extent", ctypes.c_float), ("prune_big", ctypes.c_int32)]
 
 
-def _stream(dev):
-    return _lib.stream_ptr(dev)
-
-
 def _ptr(t):
     return None if (t is None or t.numel() == 0) else t.data_ptr()
 
@@ -60,9 +56,7 @@ class _Plan:
         dst = torch.empty((self.n_out,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
         L = int(src[0].numel()) if src.shape[0] else int(torch.Size(src.shape[1:]).numel())
         if self.n_out and L:
-            with torch.cuda.device(src.device):
-                _lib.check(_lib.lib().adgs_densify_gather_rows(_ptr(src), _ptr(dst), L, self.n_out, _ptr(self.row_src), _ptr(self.row_aux), int(is_state),
-                                                               _stream(src.device)), "adgs_densify_gather_rows")
+            _lib.call("adgs_densify_gather_rows", src.device, _ptr(src), _ptr(dst), L, self.n_out, _ptr(self.row_src), _ptr(self.row_aux), int(is_state))
         return dst
 
 
@@ -83,7 +77,7 @@ def densify_and_prune(model, max_scene_grad, max_obj_grad, min_opacity, prune_bi
     i32 = dict(dtype=torch.int32, device=dev)
     sides = {}
     counts = torch.zeros(4, **i32)
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev):
         for k, (name, N, off, thr, extent, big) in enumerate((("scene", Ns, 0, max_scene_grad, model.scene_extent, 0.05),
                                                               ("obj", No, Ns, max_obj_grad, model.object_extent, 0.1))):
             scaling = getattr(model, "_%s_scaling" % name).detach().contiguous()
@@ -96,7 +90,7 @@ def densify_and_prune(model, max_scene_grad, max_obj_grad, min_opacity, prune_bi
             s.min_opacity, s.big_extent, s.prune_big = _f32(min_opacity), _f32(extent * big), int(bool(prune_big_points))
             ci, si = torch.empty(max(N, 1), **i32), torch.empty(max(N, 1), **i32)
             ws = torch.empty(lib.adgs_densify_workspace_bytes(N), dtype=torch.uint8, device=dev)
-            _lib.check(lib.adgs_densify_select(ctypes.byref(s), _ptr(ci), _ptr(si), counts[2 * k:].data_ptr(), _ptr(ws), _stream(dev)), "adgs_densify_select")
+            _lib.call("adgs_densify_select", dev, ctypes.byref(s), _ptr(ci), _ptr(si), counts[2 * k:].data_ptr(), _ptr(ws))
             sides[name] = dict(struct=s, N=N, clone_index=ci, split_index=si, scaling=scaling, opacity=opacity, keep=(accum, denom))
         n = counts.tolist()                                   # read-back 1: sizes of the normal samples
         out_counts = torch.zeros(2, **i32)
@@ -111,8 +105,8 @@ def densify_and_prune(model, max_scene_grad, max_obj_grad, min_opacity, prune_bi
             total = sd["N"] + sd["n_clone"] + 2 * sd["n_split"]
             sd["row_src"], sd["row_aux"] = torch.empty(max(total, 1), **i32), torch.empty(max(total, 1), **i32)
             ws = torch.empty(lib.adgs_densify_workspace_bytes(total), dtype=torch.uint8, device=dev)
-            _lib.check(lib.adgs_densify_plan(ctypes.byref(sd["struct"]), _ptr(sd["clone_index"]), sd["n_clone"], _ptr(sd["split_index"]), sd["n_split"],
-                                             _ptr(sd["row_src"]), _ptr(sd["row_aux"]), out_counts[k:].data_ptr(), _ptr(ws), _stream(dev)), "adgs_densify_plan")
+            _lib.call("adgs_densify_plan", dev, ctypes.byref(sd["struct"]), _ptr(sd["clone_index"]), sd["n_clone"], _ptr(sd["split_index"]), sd["n_split"],
+                      _ptr(sd["row_src"]), _ptr(sd["row_aux"]), out_counts[k:].data_ptr(), _ptr(ws))
         m = out_counts.tolist()                               # read-back 2: sizes of the new tensors
         plans = {name: _Plan(int(m[k]), sides[name]["row_src"], sides[name]["row_aux"], sides[name]["samples"]) for k, name in enumerate(("scene", "obj"))}
         _apply_plans(model, plans, dev)
@@ -121,7 +115,6 @@ def densify_and_prune(model, max_scene_grad, max_obj_grad, min_opacity, prune_bi
 
 
 def _apply_plans(model, plans, dev):
-    lib = _lib.lib()
     groups = _groups_by_name(model.optimizer)
     new_tensors = {}
     for side, names in (("scene", SCENE_GROUPS), ("obj", OBJ_GROUPS)):
@@ -133,9 +126,8 @@ def _apply_plans(model, plans, dev):
         # split children: sampled position, shrunk scale (:721-723)
         if plan.n_out:
             xyz, sc, rot = (getattr(model, "_%s_%s" % (side, k)).detach().contiguous() for k in ("xyz", "scaling", "rotation"))
-            _lib.check(lib.adgs_densify_split_rows(_ptr(xyz), _ptr(sc), _ptr(rot), _ptr(plan.samples), plan.n_out, _ptr(plan.row_src), _ptr(plan.row_aux),
-                                                   _ptr(new_tensors[side + "_xyz"]), _ptr(new_tensors[side + "_scaling"]), _stream(dev)),
-                       "adgs_densify_split_rows")
+            _lib.call("adgs_densify_split_rows", dev, _ptr(xyz), _ptr(sc), _ptr(rot), _ptr(plan.samples), plan.n_out, _ptr(plan.row_src), _ptr(plan.row_aux),
+                      _ptr(new_tensors[side + "_xyz"]), _ptr(new_tensors[side + "_scaling"]))
         for name in names:
             group = groups.get(name)
             old = getattr(model, GROUP_ATTR[name])
@@ -165,7 +157,6 @@ def _apply_plans(model, plans, dev):
 def reset_opacity(model):
     """GaussianModel.reset_opacity (:465-469): opacity = inverse_sigmoid(min(sigmoid(opacity), 0.01)) as one in-place kernel per
     side; the Adam moments of the two opacity groups are zeroed (replace_tensor_to_optimizer, :546-559)."""
-    lib = _lib.lib()
     groups = _groups_by_name(model.optimizer) if getattr(model, "optimizer", None) is not None else {}
     for name in ("scene_opacity", "obj_opacity"):
         attr = GROUP_ATTR[name]
@@ -173,8 +164,7 @@ def reset_opacity(model):
         if not old.is_cuda:
             raise RuntimeError("reset_opacity: the model must live on a HIP device; there is no CPU path")
         new = old.detach().clone().contiguous()
-        with torch.cuda.device(new.device):
-            _lib.check(lib.adgs_reset_opacity(new.numel(), _ptr(new), _stream(new.device)), "adgs_reset_opacity")
+        _lib.call("adgs_reset_opacity", new.device, new.numel(), _ptr(new))
         param = torch.nn.Parameter(new.requires_grad_(True))
         group = groups.get(name)
         if group is not None:

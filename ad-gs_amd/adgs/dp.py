@@ -192,10 +192,7 @@ def hip_sh_grad_expand(cams, W, C, P, Ns, row0, xyz_head, D, M, outs, _cache=Non
     g = _expand_grads()
     for n, t in zip(("scene_dc", "obj_dc", "scene_rest", "obj_rest", "scene_deform", "obj_deform"), outs):
         setattr(g, n, ptr(t))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().adgs_sh_grad_expand(len(cams), arr, ptr(W), int(C), int(P), int(Ns), int(row0), ptr(xyz_head), int(D), int(M),
-                                                  ctypes.byref(g), _lib.stream_ptr(dev)),
-                   "adgs_sh_grad_expand")
+    _lib.call("adgs_sh_grad_expand", dev, len(cams), arr, ptr(W), int(C), int(P), int(Ns), int(row0), ptr(xyz_head), int(D), int(M), ctypes.byref(g))
 
 
 ARENA_QUANTUM = 64 * 840
@@ -290,9 +287,7 @@ def hip_lin_grad_expand(terms, W, C, count, scale, out):
     for t in terms:
         if not (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == 3 * count):
             raise RuntimeError("adgs_lin_grad_expand: factors must be contiguous float32 [count,3]")
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().adgs_lin_grad_expand(len(terms), arr, W.data_ptr(), int(C), int(count), float(scale), out.data_ptr(),
-                                                   _lib.stream_ptr(out.device)), "adgs_lin_grad_expand")
+    _lib.call("adgs_lin_grad_expand", out.device, len(terms), arr, W.data_ptr(), int(C), int(count), float(scale), out.data_ptr())
 
 
 class _FactorSink(list):

@@ -30,9 +30,7 @@ class _EnvBackground(torch.autograd.Function):
         C, Hm, Wm = gm.shape[-3:]
         out = torch.empty(C, H, W, dtype=torch.float32, device=gm.device)
         Rarr = (ctypes.c_float * 9)(*R9)
-        with torch.cuda.device(gm.device):
-            _lib.check(_lib.lib().adgs_envmap_forward(C, Hm, Wm, gm.data_ptr(), H, W, float(focal), Rarr, out.data_ptr(),
-                                                      _lib.stream_ptr(gm.device)), "adgs_envmap_forward")
+        _lib.call("adgs_envmap_forward", gm.device, C, Hm, Wm, gm.data_ptr(), H, W, float(focal), Rarr, out.data_ptr())
         ctx.save_for_backward(out)
         ctx.meta = (tuple(grid_map.shape), C, Hm, Wm, H, W, float(focal), Rarr)
         ctx.marked = marked
@@ -47,10 +45,8 @@ class _EnvBackground(torch.autograd.Function):
         if gg is None or tuple(gg.shape) != shape or gg.device != out.device:
             gg = torch.zeros(shape, dtype=torch.float32, device=out.device)       # dense, like grid_sample's backward
         g = g.contiguous().float()
-        with torch.cuda.device(out.device):
-            _lib.check(_lib.lib().adgs_envmap_backward_marked(C, Hm, Wm, H, W, focal, Rarr, out.data_ptr(), g.data_ptr(), gg.data_ptr(),
-                                                              mk.marks.data_ptr() if mk is not None else None, ADAM_TILE,
-                                                              _lib.stream_ptr(out.device)), "adgs_envmap_backward")
+        _lib.call("adgs_envmap_backward_marked", out.device, C, Hm, Wm, H, W, focal, Rarr, out.data_ptr(), g.data_ptr(), gg.data_ptr(),
+                  mk.marks.data_ptr() if mk is not None else None, ADAM_TILE)
         if mk is not None:
             mk.issued(gg)
         return gg, None, None, None, None, None

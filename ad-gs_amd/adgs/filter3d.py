@@ -63,10 +63,7 @@ def accumulate(xyz, cams, rate, row0=0, rows=None, init=False):
         if init:
             rate.view(-1)[row0:row0 + rows].zero_()
         return rate
-    with _lib.on_device(xyz.device):
-        _lib.check(_lib.lib().adgs_filter3d_accumulate(xyz.data_ptr(), int(row0), int(rows), cams.data_ptr(),
-                                                       cams.shape[0], rate.data_ptr(), int(bool(init)), _lib.stream_ptr(xyz.device)),
-                   "adgs_filter3d_accumulate")
+    _lib.call("adgs_filter3d_accumulate", xyz.device, xyz.data_ptr(), int(row0), int(rows), cams.data_ptr(), cams.shape[0], rate.data_ptr(), int(bool(init)))
     return rate
 
 
@@ -78,9 +75,7 @@ def finalize(rate, out=None):
     N = rate.numel()
     out = torch.empty(N, 1, dtype=torch.float32, device=rate.device) if out is None else out
     work = torch.empty(1, dtype=torch.int32, device=rate.device)
-    with _lib.on_device(rate.device):
-        _lib.check(_lib.lib().adgs_filter3d_finalize(rate.data_ptr(), N, out.data_ptr(), work.data_ptr(), _lib.stream_ptr(rate.device)),
-                   "adgs_filter3d_finalize")
+    _lib.call("adgs_filter3d_finalize", rate.device, rate.data_ptr(), N, out.data_ptr(), work.data_ptr())
     return out
 
 
@@ -94,9 +89,7 @@ class _Apply(torch.autograd.Function):
                 tuple(scales.shape), tuple(opacity.shape), tuple(filter_3d.shape)))
         s, o, f = scales.contiguous().float(), opacity.contiguous().float(), filter_3d.contiguous().float()
         s_out, o_out = torch.empty_like(s), torch.empty_like(o)
-        with _lib.on_device(s.device):
-            _lib.check(_lib.lib().adgs_filter3d_apply_forward(P, s.data_ptr(), o.data_ptr(), f.data_ptr(), s_out.data_ptr(), o_out.data_ptr(),
-                                                              _lib.stream_ptr(s.device)), "adgs_filter3d_apply_forward")
+        _lib.call("adgs_filter3d_apply_forward", s.device, P, s.data_ptr(), o.data_ptr(), f.data_ptr(), s_out.data_ptr(), o_out.data_ptr())
         ctx.save_for_backward(s, o, f)
         return s_out, o_out
 
@@ -105,9 +98,8 @@ class _Apply(torch.autograd.Function):
         s, o, f = ctx.saved_tensors
         gs_out, go_out = g_s_out.contiguous().float(), g_o_out.contiguous().float()
         g_s, g_o = torch.empty_like(s), torch.empty_like(o)
-        with _lib.on_device(s.device):
-            _lib.check(_lib.lib().adgs_filter3d_apply_backward(s.shape[0], s.data_ptr(), o.data_ptr(), f.data_ptr(), gs_out.data_ptr(), go_out.data_ptr(),
-                                                               g_s.data_ptr(), g_o.data_ptr(), _lib.stream_ptr(s.device)), "adgs_filter3d_apply_backward")
+        _lib.call("adgs_filter3d_apply_backward", s.device, s.shape[0], s.data_ptr(), o.data_ptr(), f.data_ptr(), gs_out.data_ptr(), go_out.data_ptr(),
+                  g_s.data_ptr(), g_o.data_ptr())
         return g_s, g_o, None
 
 

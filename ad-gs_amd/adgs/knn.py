@@ -22,11 +22,8 @@ def knn_points(p1, p2, K=1):
     idx = torch.empty((A, K), dtype=torch.int64, device=p1.device)
     dists = torch.empty((A, K), dtype=torch.float32, device=p1.device)
     if A > 0:
-        lib = _lib.lib()
-        with torch.cuda.device(p1.device):
-            ws = torch.empty(int(lib.adgs_knn_points_workspace_bytes(A, N, K)), dtype=torch.uint8, device=p1.device)
-            _lib.check(lib.adgs_knn_points(A, a.data_ptr(), N, p.data_ptr(), D, K, idx.data_ptr(), dists.data_ptr(), ws.data_ptr(),
-                                           _lib.stream_ptr(p1.device)), "adgs_knn_points")
+        ws = torch.empty(int(_lib.lib().adgs_knn_points_workspace_bytes(A, N, K)), dtype=torch.uint8, device=p1.device)
+        _lib.call("adgs_knn_points", p1.device, A, a.data_ptr(), N, p.data_ptr(), D, K, idx.data_ptr(), dists.data_ptr(), ws.data_ptr())
     return _KNN(dists[None], idx[None], None)
 
 

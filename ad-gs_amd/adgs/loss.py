@@ -16,10 +16,6 @@ from . import _lib
 SLOTS = 256        # ADGS_LOSS_SLOTS
 
 
-def _stream(dev):
-    return _lib.stream_ptr(dev)
-
-
 class _Slice:
     """Ownership of one slice of a _WorkArena (or of nothing: a fresh buffer).  The slot is free again when the token is dropped -- at once
     for terms whose backward does not read the slice, with the autograd context for the terms whose backward does (depth, flow).  A token
@@ -93,6 +89,37 @@ def _work(device, doubles):
     return torch.zeros(doubles, dtype=torch.float64, device=device), t
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _scalar(device, launched, n=1):
+    """The [n] fp32 output of a term: written by its kernels when they are launched, zeros for an empty input (no launch)."""
+    return (torch.empty if launched else torch.zeros)(n, dtype=torch.float32, device=device)
+
+
+def _g1(g_loss):
+    """The upstream gradient of a scalar term as one contiguous fp32 element."""
+    return None if g_loss is None else g_loss.reshape(1).float().contiguous()
+
+
+# An image term is ONE pair of plain functions that owns the term's whole marshalling -- work slice, native call(s), done() -- over prepared contiguous
+# fp32 tensors and raw output / gradient POINTERS: a standalone Function hands in a small tensor's pointer, the fused _ImageLosses node an element of its [6].
+def _l1_ssim_fwd(img, ref, maps, out2):
+    H, W = img.shape[-2:]
+    sums, tok = _work(img.device, 2 * SLOTS)                   # spread atomics (include/adgs_loss.h); consumed by adgs_l1_ssim_means below
+    if img.numel():
+        _lib.call("adgs_l1_ssim_forward", img.device, img.numel() // (H * W), H, W, img.data_ptr(), ref.data_ptr(), sums.data_ptr(), *[_ptr(m) for m in maps])
+        _lib.call("adgs_l1_ssim_means", img.device, sums.data_ptr(), img.numel(), out2)
+    tok.done()
+
+
+def _l1_ssim_bwd(img, ref, maps, g_l1, g_ssim, out):
+    H, W = img.shape[-2:]
+    if img.numel():
+        _lib.call("adgs_l1_ssim_backward", img.device, img.numel() // (H * W), H, W, img.data_ptr(), ref.data_ptr(), *[m.data_ptr() for m in maps], g_l1, g_ssim, out)
+
+
 class _L1SSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt):
@@ -101,38 +128,19 @@ class _L1SSIM(torch.autograd.Function):
         if image.shape != gt.shape or image.dim() < 3:
             raise ValueError("l1_ssim: image and gt must have the same [..., C, H, W] shape")
         img, ref = image.contiguous().float(), gt.contiguous().float()
-        H, W = img.shape[-2:]
-        planes = img.numel() // (H * W) if H * W else 0
-        n = img.numel()
         need = ctx.needs_input_grad[0]
-        sums, tok = _work(img.device, 2 * SLOTS)                   # spread atomics (include/adgs_loss.h); consumed by adgs_l1_ssim_means below
         maps = [torch.empty_like(img) for _ in range(3)] if need else [None] * 3
-        means = torch.empty(2, dtype=torch.float32, device=img.device) if n else torch.zeros(2, dtype=torch.float32, device=img.device)
-        if n:
-            with torch.cuda.device(img.device):
-                _lib.check(_lib.lib().adgs_l1_ssim_forward(planes, H, W, img.data_ptr(), ref.data_ptr(), sums.data_ptr(),
-                                                           *[m.data_ptr() if m is not None else None for m in maps], _stream(img.device)),
-                           "adgs_l1_ssim_forward")
-                _lib.check(_lib.lib().adgs_l1_ssim_means(sums.data_ptr(), n, means.data_ptr(), _stream(img.device)), "adgs_l1_ssim_means")
-        tok.done()
+        means = _scalar(img.device, img.numel(), 2)
+        _l1_ssim_fwd(img, ref, maps, means.data_ptr())
         if need:
             ctx.save_for_backward(img, ref, *maps)
-        ctx.dims = (planes, H, W)
         return means[0], means[1]
 
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
-        img, ref, d_mu1, d_e11, d_e12 = ctx.saved_tensors
-        planes, H, W = ctx.dims
-        out = torch.empty_like(img)
-        gl = g_l1.reshape(1).float().contiguous() if g_l1 is not None else None
-        gs = g_ssim.reshape(1).float().contiguous() if g_ssim is not None else None
-        if img.numel():
-            with torch.cuda.device(img.device):
-                _lib.check(_lib.lib().adgs_l1_ssim_backward(planes, H, W, img.data_ptr(), ref.data_ptr(), d_mu1.data_ptr(), d_e11.data_ptr(),
-                                                            d_e12.data_ptr(), gl.data_ptr() if gl is not None else None,
-                                                            gs.data_ptr() if gs is not None else None, out.data_ptr(), _stream(img.device)),
-                           "adgs_l1_ssim_backward")
+        img, ref, *maps = ctx.saved_tensors
+        out, gl, gs = torch.empty_like(img), _g1(g_l1), _g1(g_ssim)
+        _l1_ssim_bwd(img, ref, maps, _ptr(gl), _ptr(gs), out.data_ptr())
         return out, None
 
 
@@ -163,6 +171,18 @@ def photometric_loss(image, gt, lambda_dssim, lambda_l1=1.0):
 DEPTH_WORK_DOUBLES = 256 * 8 + 16        # ADGS_DEPTH_WORK_DOUBLES
 
 
+def _depth_fwd(p, g, m, out):
+    """-> (work, token): the backward reads the fitted scale and shift from `work`, so both live with the autograd context."""
+    work, tok = _work(p.device, DEPTH_WORK_DOUBLES)
+    _lib.call("adgs_depth_loss_forward", p.device, p.numel(), p.data_ptr(), g.data_ptr(), _ptr(m), work.data_ptr(), out)
+    tok.done()
+    return work, tok
+
+
+def _depth_bwd(p, g, m, work, g_loss, out):
+    _lib.call("adgs_depth_loss_backward", p.device, p.numel(), p.data_ptr(), g.data_ptr(), _ptr(m), work.data_ptr(), g_loss, out)
+
+
 class _DepthLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, mask):
@@ -172,24 +192,16 @@ class _DepthLoss(torch.autograd.Function):
         m = None if mask is None else mask.contiguous().float()
         if p.shape != g.shape or (m is not None and m.shape != p.shape):
             raise ValueError("get_depth_loss: prediction, target and mask must have the same shape")
-        work, ctx.token = _work(p.device, DEPTH_WORK_DOUBLES)
-        out = torch.empty(1, dtype=torch.float32, device=p.device) if p.numel() else torch.zeros(1, dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().adgs_depth_loss_forward(p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else None,
-                                                          work.data_ptr(), out.data_ptr(), _stream(p.device)), "adgs_depth_loss_forward")
-        ctx.token.done()
+        out = _scalar(p.device, p.numel())
+        work, ctx.token = _depth_fwd(p, g, m, out.data_ptr())
         ctx.save_for_backward(p, g, work, *([m] if m is not None else []))
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         p, g, work, *rest = ctx.saved_tensors
-        m = rest[0] if rest else None
-        out = torch.empty_like(p)
-        gl = g_loss.reshape(1).float().contiguous()
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().adgs_depth_loss_backward(p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else None,
-                                                           work.data_ptr(), gl.data_ptr(), out.data_ptr(), _stream(p.device)), "adgs_depth_loss_backward")
+        out, gl = torch.empty_like(p), _g1(g_loss)
+        _depth_bwd(p, g, rest[0] if rest else None, work, gl.data_ptr(), out.data_ptr())
         return out, None, None
 
 
@@ -222,11 +234,21 @@ class _FlowCam:
             self.keep = None
             self.args = tuple((ctypes.c_float * n)(*[float(x) for x in t.detach().reshape(-1).tolist()]) for t, n in zip(ts, (9, 9, 3)))
 
-    def forward_fn(self):
-        return _lib.lib().adgs_flow_loss_forward_devcam if self.on_device else _lib.lib().adgs_flow_loss_forward
+    def symbol(self, direction):
+        return "adgs_flow_loss_%s%s" % (direction, "_devcam" if self.on_device else "")
 
-    def backward_fn(self):
-        return _lib.lib().adgs_flow_loss_backward_devcam if self.on_device else _lib.lib().adgs_flow_loss_backward
+
+def _flow_fwd(cam, f, fl, vis, op, dist, out):
+    """-> (work, token): the backward reads the number of valid pixels from `work`, so both live with the autograd context."""
+    work, tok = _work(f.device, AUX_WORK_DOUBLES)
+    _lib.call(cam.symbol("forward"), f.device, fl.shape[1], fl.shape[2], f.data_ptr(), fl.data_ptr(), vis.data_ptr(), _ptr(op), *cam.args, dist, work.data_ptr(), out)
+    tok.done()
+    return work, tok
+
+
+def _flow_bwd(cam, f, fl, vis, op, dist, work, g_loss, g_f, g_op):
+    _lib.call(cam.symbol("backward"), f.device, fl.shape[1], fl.shape[2], f.data_ptr(), fl.data_ptr(), vis.data_ptr(), _ptr(op), *cam.args, dist, work.data_ptr(),
+              g_loss, g_f, g_op)
 
 
 class _FlowLoss(torch.autograd.Function):
@@ -241,13 +263,8 @@ class _FlowLoss(torch.autograd.Function):
         if f.shape != (3, H, W) or fl.shape[0] != 2 or vis.shape != (H, W) or (op is not None and op.numel() != H * W):
             raise ValueError("get_flow_loss: expected img_flow [3,H,W], flow [2,H,W], flow_vis [H,W], img_opacity [H,W]")
         cam = _FlowCam(K, R, T, f.device)
-        work, ctx.token = _work(f.device, AUX_WORK_DOUBLES)
-        out = torch.empty(1, dtype=torch.float32, device=f.device) if H * W else torch.zeros(1, dtype=torch.float32, device=f.device)
-        with torch.cuda.device(f.device):
-            _lib.check(cam.forward_fn()(H, W, f.data_ptr(), fl.data_ptr(), vis.data_ptr(), op.data_ptr() if op is not None else None,
-                                        cam.args[0], cam.args[1], cam.args[2], float(dist), work.data_ptr(), out.data_ptr(), _stream(f.device)),
-                       "adgs_flow_loss_forward")
-        ctx.token.done()
+        out = _scalar(f.device, H * W)
+        work, ctx.token = _flow_fwd(cam, f, fl, vis, op, float(dist), out.data_ptr())
         ctx.save_for_backward(f, fl, vis, work, *([op] if op is not None else []))
         ctx.cam, ctx.dist, ctx.op_shape = cam, float(dist), None if img_opacity is None else img_opacity.shape
         return out[0]
@@ -256,14 +273,10 @@ class _FlowLoss(torch.autograd.Function):
     def backward(ctx, g_loss):
         f, fl, vis, work, *rest = ctx.saved_tensors
         op = rest[0] if rest else None
-        H, W = fl.shape[1], fl.shape[2]
         g_f = torch.empty_like(f)
-        g_op = torch.empty(H, W, dtype=torch.float32, device=f.device) if op is not None else None
-        gl = g_loss.reshape(1).float().contiguous()
-        with torch.cuda.device(f.device):
-            _lib.check(ctx.cam.backward_fn()(H, W, f.data_ptr(), fl.data_ptr(), vis.data_ptr(), op.data_ptr() if op is not None else None,
-                                             ctx.cam.args[0], ctx.cam.args[1], ctx.cam.args[2], ctx.dist, work.data_ptr(), gl.data_ptr(), g_f.data_ptr(),
-                                             g_op.data_ptr() if g_op is not None else None, _stream(f.device)), "adgs_flow_loss_backward")
+        g_op = torch.empty(fl.shape[1:], dtype=torch.float32, device=f.device) if op is not None else None
+        gl = _g1(g_loss)
+        _flow_bwd(ctx.cam, f, fl, vis, op, ctx.dist, work, gl.data_ptr(), g_f.data_ptr(), _ptr(g_op))
         return g_f, (g_op.reshape(ctx.op_shape) if g_op is not None else None), None, None, None, None, None, None
 
 
@@ -276,6 +289,17 @@ def get_flow_loss(img_flow, flow_pkg, img_opacity=None, dist=1e-3):
     return _FlowLoss.apply(img_flow, img_opacity, flow.detach(), flow_vis.detach(), K, R, T, dist)
 
 
+def _bce_fwd(p, t, params, out):
+    """params: (lo, hi, invert, positive_target) as the native entry takes them."""
+    work, tok = _work(p.device, AUX_WORK_DOUBLES)
+    _lib.call("adgs_bce_clip_forward", p.device, p.numel(), p.data_ptr(), t.data_ptr(), *params, work.data_ptr(), out)
+    tok.done()
+
+
+def _bce_bwd(p, t, params, g_loss, out):
+    _lib.call("adgs_bce_clip_backward", p.device, p.numel(), p.data_ptr(), t.data_ptr(), *params, g_loss, out)
+
+
 class _BceClip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, lo, hi, invert, positive_target):
@@ -284,25 +308,17 @@ class _BceClip(torch.autograd.Function):
         p, t = pred.contiguous().float(), target.contiguous().float()
         if p.numel() != t.numel():
             raise ValueError("bce_clip_loss: prediction and target must have the same number of elements")
-        work, tok = _work(p.device, AUX_WORK_DOUBLES)
-        out = torch.empty(1, dtype=torch.float32, device=p.device) if p.numel() else torch.zeros(1, dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().adgs_bce_clip_forward(p.numel(), p.data_ptr(), t.data_ptr(), float(lo), float(hi), int(bool(invert)),
-                                                        int(bool(positive_target)), work.data_ptr(), out.data_ptr(), _stream(p.device)), "adgs_bce_clip_forward")
-        tok.done()
+        ctx.params, ctx.shape = (float(lo), float(hi), int(bool(invert)), int(bool(positive_target))), pred.shape
+        out = _scalar(p.device, p.numel())
+        _bce_fwd(p, t, ctx.params, out.data_ptr())
         ctx.save_for_backward(p, t)
-        ctx.args, ctx.shape = (float(lo), float(hi), int(bool(invert)), int(bool(positive_target))), pred.shape
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         p, t = ctx.saved_tensors
-        out = torch.empty_like(p)
-        gl = g_loss.reshape(1).float().contiguous()
-        lo, hi, inv, pos = ctx.args
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().adgs_bce_clip_backward(p.numel(), p.data_ptr(), t.data_ptr(), lo, hi, inv, pos, gl.data_ptr(), out.data_ptr(),
-                                                         _stream(p.device)), "adgs_bce_clip_backward")
+        out, gl = torch.empty_like(p), _g1(g_loss)
+        _bce_bwd(p, t, ctx.params, gl.data_ptr(), out.data_ptr())
         return out.reshape(ctx.shape), None, None, None, None, None
 
 
@@ -311,14 +327,19 @@ def bce_clip_loss(pred, target, lo=1e-3, hi=1.0 - 1e-3, invert=False, positive_t
     return _BceClip.apply(pred, target.detach(), lo, hi, invert, positive_target)
 
 
+# (lo, hi, invert, positive_target) of the two BCE terms of a training iteration: obj_loss, sky_loss and the fused _ImageLosses node read these
+OBJ_BCE = (1e-3, 1.0 - 1e-3, 0, 1)
+SKY_BCE = (1e-3, 1.0 - 1e-3, 1, 0)
+
+
 def obj_loss(img_semantic, gt_semantic):
     """train.py:95-98: binary_cross_entropy(clip(img_semantic, 1e-3, 1 - 1e-3)[0], (gt_semantic > 0).float())."""
-    return bce_clip_loss(img_semantic[0] if img_semantic.dim() == 3 else img_semantic, gt_semantic, positive_target=True)
+    return bce_clip_loss(img_semantic[0] if img_semantic.dim() == 3 else img_semantic, gt_semantic, *OBJ_BCE)
 
 
 def sky_loss(img_opacity, gt_sky):
     """train.py:100-103: binary_cross_entropy(1 - clip(img_opacity, 1e-3, 1 - 1e-3), gt_sky)."""
-    return bce_clip_loss(img_opacity, gt_sky, invert=True)
+    return bce_clip_loss(img_opacity, gt_sky, *SKY_BCE)
 
 
 # ---------------------------------------------------------------- neighbourhood regularisers (train.py:104-113)
@@ -351,27 +372,21 @@ class _GroupVar(torch.autograd.Function):
         N = xs.shape[0]
         D = xs.numel() // max(N, 1)
         G, K = ix.shape
+        ctx.dims, ctx.shape = (N, G, K, D, int(inner)), x.shape
         work, tok = _work(xs.device, AUX_WORK_DOUBLES)
-        out = torch.empty(1, dtype=torch.float32, device=xs.device) if (G and D) else torch.zeros(1, dtype=torch.float32, device=xs.device)
+        out = _scalar(xs.device, G and D)
         if G and D:
-            with torch.cuda.device(xs.device):
-                _lib.check(_lib.lib().adgs_group_var_forward(N, G, K, D, int(inner), xs.data_ptr(), ix.data_ptr(), work.data_ptr(), out.data_ptr(),
-                                                             _stream(xs.device)), "adgs_group_var_forward")
+            _lib.call("adgs_group_var_forward", xs.device, *ctx.dims, xs.data_ptr(), ix.data_ptr(), work.data_ptr(), out.data_ptr())
         tok.done()
         ctx.save_for_backward(xs, ix)
-        ctx.dims, ctx.shape = (N, G, K, D, int(inner)), x.shape
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         xs, ix = ctx.saved_tensors
-        N, G, K, D, inner = ctx.dims
-        out = torch.zeros_like(xs)
-        gl = g_loss.reshape(1).float().contiguous()
-        if G and D:
-            with torch.cuda.device(xs.device):
-                _lib.check(_lib.lib().adgs_group_var_backward(N, G, K, D, inner, xs.data_ptr(), ix.data_ptr(), gl.data_ptr(), out.data_ptr(),
-                                                              _stream(xs.device)), "adgs_group_var_backward")
+        out, gl = torch.zeros_like(xs), _g1(g_loss)
+        if ctx.dims[1] and ctx.dims[3]:
+            _lib.call("adgs_group_var_backward", xs.device, *ctx.dims, xs.data_ptr(), ix.data_ptr(), gl.data_ptr(), out.data_ptr())
         return out.reshape(ctx.shape), None, None
 
 
@@ -393,26 +408,21 @@ class _SigmaLoss(torch.autograd.Function):
         if log_sigma.dim() != 2 or log_sigma.shape[1] != 2:
             raise ValueError("gs_time_sigma must be [N, 2]")
         ls = log_sigma.contiguous().float()
+        ctx.gap = float(frame_gap)
         work, tok = _work(ls.device, AUX_WORK_DOUBLES)
-        out = torch.empty(1, dtype=torch.float32, device=ls.device) if ls.shape[0] else torch.zeros(1, dtype=torch.float32, device=ls.device)
+        out = _scalar(ls.device, ls.shape[0])
         if ls.shape[0]:
-            with torch.cuda.device(ls.device):
-                _lib.check(_lib.lib().adgs_sigma_loss_forward(ls.shape[0], ls.data_ptr(), float(frame_gap), work.data_ptr(), out.data_ptr(),
-                                                              _stream(ls.device)), "adgs_sigma_loss_forward")
+            _lib.call("adgs_sigma_loss_forward", ls.device, ls.shape[0], ls.data_ptr(), ctx.gap, work.data_ptr(), out.data_ptr())
         tok.done()
         ctx.save_for_backward(ls)
-        ctx.gap = float(frame_gap)
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         (ls,) = ctx.saved_tensors
-        out = torch.empty_like(ls)
-        gl = g_loss.reshape(1).float().contiguous()
+        out, gl = torch.empty_like(ls), _g1(g_loss)
         if ls.shape[0]:
-            with torch.cuda.device(ls.device):
-                _lib.check(_lib.lib().adgs_sigma_loss_backward(ls.shape[0], ls.data_ptr(), ctx.gap, gl.data_ptr(), out.data_ptr(), _stream(ls.device)),
-                           "adgs_sigma_loss_backward")
+            _lib.call("adgs_sigma_loss_backward", ls.device, ls.shape[0], ls.data_ptr(), ctx.gap, gl.data_ptr(), out.data_ptr())
         return out, None
 
 
@@ -458,24 +468,20 @@ def weighted_total(terms):
 
 # ---------------------------------------------------------------- the image terms of train.py:78-99 as ONE autograd node
 class _ImageLosses(torch.autograd.Function):
-    """L1, SSIM, depth loss, flow loss, object BCE, sky BCE -- the same kernels, the same work buffers as the six functions above, behind
+    """L1, SSIM, depth loss, flow loss, object BCE, sky BCE -- the `_*_fwd` / `_*_bwd` pairs of the six functions above, in their order, behind
     one autograd node: six Python-level Function calls forward and six backward (each ~30 us of host time around a 5 - 90 us kernel)
     become two, so the short kernels of this section no longer wait for the host between them (tools/iteration_gaps.py: ~100 us of
     idle GPU per iteration in front of the rasterizer's backward).  Output: a [6] tensor (Ll1, ssim, depth, flow, obj, sky)."""
 
     @staticmethod
     def forward(ctx, image, depth, img_flow, img_opacity, img_semantic, gt_image, gt_depth, flow, flow_vis, cam, dist, gt_semantic, gt_sky):
-        dev = image.device
         if not image.is_cuda:
             raise RuntimeError("image_losses: tensors must be on a HIP device; there is no CPU path")
-        L = _lib.lib()
-        st = _stream(dev)
         f32 = lambda t: t.contiguous().float()
         img, ref = f32(image), f32(gt_image)
         H, W = img.shape[-2:]
         if img.shape != ref.shape or img.dim() != 3:
             raise ValueError("image_losses: image and gt_image must be [C, H, W]")
-        npix = H * W
         dep, gdep = f32(depth).reshape(H, W), f32(gt_depth).reshape(H, W)
         fl_img, op = f32(img_flow), f32(img_opacity).reshape(H, W)
         fl, vis = f32(flow), f32(flow_vis)
@@ -483,24 +489,14 @@ class _ImageLosses(torch.autograd.Function):
         gsem, gsky = f32(gt_semantic).reshape(H, W), f32(gt_sky).reshape(H, W)
         if fl_img.shape != (3, H, W) or fl.shape != (2, H, W) or vis.shape != (H, W):
             raise ValueError("image_losses: expected img_flow [3,H,W], flow [2,H,W], flow_vis [H,W]")
-        terms = torch.empty(6, dtype=torch.float32, device=dev)
+        terms = _scalar(img.device, img.numel(), 6)
         maps = [torch.empty_like(img) for _ in range(3)]
-        sums, tok_sums = _work(dev, 2 * SLOTS)
-        w_depth, tok_depth = _work(dev, DEPTH_WORK_DOUBLES)
-        w_flow, tok_flow = _work(dev, AUX_WORK_DOUBLES)
-        w_obj, tok_obj = _work(dev, AUX_WORK_DOUBLES)
-        w_sky, tok_sky = _work(dev, AUX_WORK_DOUBLES)
         p0 = terms.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(L.adgs_l1_ssim_forward(img.shape[0], H, W, img.data_ptr(), ref.data_ptr(), sums.data_ptr(), *[m.data_ptr() for m in maps], st), "adgs_l1_ssim_forward")
-            _lib.check(L.adgs_l1_ssim_means(sums.data_ptr(), img.numel(), p0, st), "adgs_l1_ssim_means")
-            _lib.check(L.adgs_depth_loss_forward(npix, dep.data_ptr(), gdep.data_ptr(), None, w_depth.data_ptr(), p0 + 8, st), "adgs_depth_loss_forward")
-            _lib.check(cam.forward_fn()(H, W, fl_img.data_ptr(), fl.data_ptr(), vis.data_ptr(), op.data_ptr(), cam.args[0], cam.args[1], cam.args[2], float(dist),
-                                        w_flow.data_ptr(), p0 + 12, st), "adgs_flow_loss_forward")
-            _lib.check(L.adgs_bce_clip_forward(npix, sem.data_ptr(), gsem.data_ptr(), 1e-3, 1.0 - 1e-3, 0, 1, w_obj.data_ptr(), p0 + 16, st), "adgs_bce_clip_forward")
-            _lib.check(L.adgs_bce_clip_forward(npix, op.data_ptr(), gsky.data_ptr(), 1e-3, 1.0 - 1e-3, 1, 0, w_sky.data_ptr(), p0 + 20, st), "adgs_bce_clip_forward")
-        for tok in (tok_sums, tok_depth, tok_flow, tok_obj, tok_sky):
-            tok.done()
+        _l1_ssim_fwd(img, ref, maps, p0)
+        w_depth, tok_depth = _depth_fwd(dep, gdep, None, p0 + 8)
+        w_flow, tok_flow = _flow_fwd(cam, fl_img, fl, vis, op, float(dist), p0 + 12)
+        _bce_fwd(sem, gsem, OBJ_BCE, p0 + 16)
+        _bce_fwd(op, gsky, SKY_BCE, p0 + 20)
         ctx.save_for_backward(img, ref, *maps, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky)
         ctx.tokens, ctx.cam, ctx.dist = (tok_depth, tok_flow), cam, float(dist)
         ctx.shapes = (image.shape, depth.shape, img_flow.shape, img_opacity.shape, img_semantic.shape)
@@ -508,31 +504,21 @@ class _ImageLosses(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (img, ref, d_mu1, d_e11, d_e12, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky) = ctx.saved_tensors
-        dev = img.device
-        L = _lib.lib()
-        st = _stream(dev)
-        H, W = img.shape[-2:]
-        npix = H * W
+        img, ref, d_mu1, d_e11, d_e12, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky = ctx.saved_tensors
         g = g.contiguous().float()
         p0 = g.data_ptr()
         g_img, g_dep, g_fl = torch.empty_like(img), torch.empty_like(dep), torch.empty_like(fl_img)
         g_op, g_op2, g_sem = torch.empty_like(op), torch.empty_like(op), torch.empty_like(sem)
-        with torch.cuda.device(dev):
-            _lib.check(L.adgs_l1_ssim_backward(img.shape[0], H, W, img.data_ptr(), ref.data_ptr(), d_mu1.data_ptr(), d_e11.data_ptr(), d_e12.data_ptr(),
-                                               p0, p0 + 4, g_img.data_ptr(), st), "adgs_l1_ssim_backward")
-            _lib.check(L.adgs_depth_loss_backward(npix, dep.data_ptr(), gdep.data_ptr(), None, w_depth.data_ptr(), p0 + 8, g_dep.data_ptr(), st), "adgs_depth_loss_backward")
-            _lib.check(ctx.cam.backward_fn()(H, W, fl_img.data_ptr(), fl.data_ptr(), vis.data_ptr(), op.data_ptr(), ctx.cam.args[0], ctx.cam.args[1], ctx.cam.args[2], ctx.dist,
-                                             w_flow.data_ptr(), p0 + 12, g_fl.data_ptr(), g_op.data_ptr(), st), "adgs_flow_loss_backward")
-            _lib.check(L.adgs_bce_clip_backward(npix, sem.data_ptr(), gsem.data_ptr(), 1e-3, 1.0 - 1e-3, 0, 1, p0 + 16, g_sem.data_ptr(), st), "adgs_bce_clip_backward")
-            _lib.check(L.adgs_bce_clip_backward(npix, op.data_ptr(), gsky.data_ptr(), 1e-3, 1.0 - 1e-3, 1, 0, p0 + 20, g_op2.data_ptr(), st), "adgs_bce_clip_backward")
+        _l1_ssim_bwd(img, ref, (d_mu1, d_e11, d_e12), p0, p0 + 4, g_img.data_ptr())
+        _depth_bwd(dep, gdep, None, w_depth, p0 + 8, g_dep.data_ptr())
+        _flow_bwd(ctx.cam, fl_img, fl, vis, op, ctx.dist, w_flow, p0 + 12, g_fl.data_ptr(), g_op.data_ptr())
+        _bce_bwd(sem, gsem, OBJ_BCE, p0 + 16, g_sem.data_ptr())
+        _bce_bwd(op, gsky, SKY_BCE, p0 + 20, g_op2.data_ptr())
         g_op.add_(g_op2)                               # img_opacity feeds the flow loss and the sky loss
         s_img, s_dep, s_fl, s_op, s_sem = ctx.shapes
-        if len(s_sem) == 3:                            # [D_S, H, W]: only channel 0 enters the object loss (train.py:95-98)
-            full = torch.zeros(s_sem, dtype=torch.float32, device=dev) if s_sem[0] > 1 else None
-            g_sem_out = g_sem.reshape(1, H, W) if full is None else full
-            if full is not None:
-                full[0].copy_(g_sem)
+        if len(s_sem) == 3 and s_sem[0] > 1:           # [D_S, H, W]: only channel 0 enters the object loss (train.py:95-98)
+            g_sem_out = torch.zeros(s_sem, dtype=torch.float32, device=img.device)
+            g_sem_out[0].copy_(g_sem)
         else:
             g_sem_out = g_sem.reshape(s_sem)
         return (g_img.reshape(s_img), g_dep.reshape(s_dep), g_fl.reshape(s_fl), g_op.reshape(s_op), g_sem_out) + (None,) * 8

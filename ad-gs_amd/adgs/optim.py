@@ -366,18 +366,16 @@ class FusedAdam(torch.optim.Optimizer):
                     if group.get("visibility_rows") is not None:     # cannot happen: _visibility_rows saw every gradient this loop sees
                         raise RuntimeError("FusedAdam.step(visibility=): group %r is marked for the masked step but has no row table" % (group.get("name"),))
                     rows[id(p)] = AdamRows(None, 0, 1, ROWS_DENSE)
-        lib = _lib.lib()
         for (dev, b1, b2, eps), items in batches.items():
-            with torch.cuda.device(dev):
-                stream = _lib.stream_ptr(dev)
+            with _lib.on_device(dev):
                 for i in range(0, len(items), MAX_GROUPS):
                     chunk = items[i:i + MAX_GROUPS]
                     arr = (AdamGroup * len(chunk))(*[c[0] for c in chunk])
                     if rows is None:
-                        _lib.check(lib.adgs_adam_step(arr, len(chunk), b1, b2, eps, int(fill), stream), "adgs_adam_step")
+                        _lib.call("adgs_adam_step", dev, arr, len(chunk), b1, b2, eps, int(fill))
                     else:
                         vis = (AdamRows * len(chunk))(*[rows[id(c[1])] for c in chunk])
-                        _lib.check(lib.adgs_adam_step_rows(arr, vis, len(chunk), b1, b2, eps, int(fill), stream), "adgs_adam_step_rows")
+                        _lib.call("adgs_adam_step_rows", dev, arr, vis, len(chunk), b1, b2, eps, int(fill))
             for _, p, g in items:
                 if fill and g is not p.grad:
                     p.grad.zero_()          # the kernel zeroed the contiguous copy
@@ -434,7 +432,5 @@ def add_densification_stats(xyz_gradient_accum, denom, max_radii2D, viewspace_gr
     N = radii.numel()
     if xyz_gradient_accum.numel() != N or denom.numel() != N or (max_radii2D is not None and max_radii2D.numel() != N):
         raise ValueError("add_densification_stats: accumulator sizes do not match the number of Gaussians")
-    with torch.cuda.device(radii.device):
-        _lib.check(_lib.lib().adgs_densification_stats(N, radii.data_ptr(), viewspace_grad.data_ptr(), xyz_gradient_accum.data_ptr(), denom.data_ptr(),
-                                                       max_radii2D.data_ptr() if max_radii2D is not None else None,
-                                                       _lib.stream_ptr(radii.device)), "adgs_densification_stats")
+    _lib.call("adgs_densification_stats", radii.device, N, radii.data_ptr(), viewspace_grad.data_ptr(), xyz_gradient_accum.data_ptr(), denom.data_ptr(),
+              max_radii2D.data_ptr() if max_radii2D is not None else None)

@@ -13,14 +13,11 @@ from adgs import _lib
 def distCUDA2(points):
     if not points.is_cuda:
         raise RuntimeError("distCUDA2: points must be on a HIP device; there is no CPU path")
-    lib = _lib.lib()
     P = points.size(0)
     pts = points.contiguous().float()
     means = torch.zeros((P,), dtype=torch.float32, device=points.device)
     if P == 0:
         return means
-    with torch.cuda.device(points.device):
-        ws = torch.empty((int(lib.adgs_knn_workspace_bytes(P)),), dtype=torch.uint8, device=points.device)
-        stream = _lib.stream_ptr(points.device)
-        _lib.check(lib.adgs_knn_dist2(P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), stream), "adgs_knn_dist2")
+    ws = torch.empty((int(_lib.lib().adgs_knn_workspace_bytes(P)),), dtype=torch.uint8, device=points.device)
+    _lib.call("adgs_knn_dist2", points.device, P, pts.data_ptr(), means.data_ptr(), ws.data_ptr())
     return means
