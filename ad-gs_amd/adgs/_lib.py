@@ -129,6 +129,9 @@ SIGNATURES = {
     "adgs_filter3d_finalize": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "adgs_filter3d_apply_forward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_filter3d_apply_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_metrics.h
+    "adgs_metrics_work_doubles": (ctypes.c_size_t, [c_i]),
+    "adgs_metrics_accumulate": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
