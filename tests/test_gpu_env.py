@@ -81,6 +81,11 @@ def test_random_maps_cameras_and_image_shapes_vs_oracle(seed):
     assert bad.sum() <= max(3, 1e-3 * bad.size), (Hm, Wm, H, W, int(bad.sum()), float(np.abs(got - ref).max()))   # a sample on a texel edge may round across it
     gbad = np.abs(gm.grad.cpu().numpy()[0] - gref) > 1e-4 * max(np.abs(gref).max(), 1.0) + tol * np.abs(wts).max() * 4
     assert gbad.sum() <= max(6, 2e-3 * gbad.size), (Hm, Wm, H, W, int(gbad.sum()))
+    # the allowance above is for pixels on the azimuth seam or the pole, where the sample position jumps; everywhere else there is
+    # no outlier (measured on an MI355X over seeds 0..39: none, the largest error 5 % of the tolerance; tests/test_gpu_env_paths.py)
+    unstable = env_oracle.unstable_pixels(H, W, focal, R, 1e-5)
+    assert not (bad & ~unstable).any(), (Hm, Wm, H, W, int((bad & ~unstable).sum()))
+    assert unstable.any() or not gbad.any(), (Hm, Wm, H, W, int(gbad.sum()))
 
 
 def _env_cam(yaw, pitch, cid, W=640, H=400):
