@@ -88,6 +88,8 @@ SIGNATURES = {
     "adgs_l1_ssim_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_l1_ssim_means": (c_i, [c_p, ctypes.c_longlong, c_p, c_p]),
     "adgs_l1_ssim_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_l1_ssim_weighted_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_l1_ssim_weighted_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_depth_loss_forward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_depth_loss_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_flow_loss_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
@@ -96,6 +98,10 @@ SIGNATURES = {
     "adgs_flow_loss_backward_devcam": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
     "adgs_bce_clip_forward": (c_i, [c_i, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p]),
     "adgs_bce_clip_backward": (c_i, [c_i, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p]),
+    "adgs_bce_clip_weighted_forward": (c_i, [c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p]),
+    "adgs_bce_clip_weighted_backward": (c_i, [c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "adgs_lidar_depth_loss_forward": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "adgs_lidar_depth_loss_backward": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
     "adgs_group_var_forward": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_group_var_backward": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_sigma_loss_forward": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p]),

@@ -5,6 +5,9 @@ utils/loss_utils.py `l1_loss` (:20-21) and `ssim` (:37-68) as used at train.py:7
 kernel (adgs_l1_ssim_forward / _backward, include/adgs_loss.h); `l1_loss` / `ssim` keep the reference's
 names and signatures on top of it.  Images are [..., C, H, W] fp32 on a HIP device, `gt` is a constant.
 There is no CPU fallback.
+
+Every image term takes an optional per-pixel supervision weight (`weight=`: ego vehicle, invalid borders of undistorted images, excluded
+regions) -- see l1_ssim -- and `lidar_depth_loss` is the sparse metric depth term over the lidar_depth/*.npz arrays.
 """
 import ctypes
 import threading
@@ -144,26 +147,98 @@ class _L1SSIM(torch.autograd.Function):
         return out, None
 
 
-def l1_ssim(image, gt):
-    """(mean |image - gt|, mean SSIM(image, gt)) -- both differentiable w.r.t. `image`."""
-    return _L1SSIM.apply(image, gt.detach())
+L1_SSIM_WEIGHTED_WORK_DOUBLES = 256 * 3 + 4        # ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES
 
 
-def l1_loss(network_output, gt):
-    """utils/loss_utils.py:20-21."""
-    return l1_ssim(network_output, gt)[0]
+def _check_weight(weight, H, W, device, who):
+    """A supervision weight as the kernels take it: a float32 [H, W] (or [1, H, W]) tensor on `device`, detached and contiguous.
+    Decided from the arguments alone, before anything is launched; the range [0, 1] is not checked (that would be a read-back)."""
+    if not torch.is_tensor(weight):
+        raise TypeError("%s: weight must be a tensor, got %s" % (who, type(weight).__name__))
+    if tuple(weight.shape) not in ((H, W), (1, H, W)):
+        raise ValueError("%s: weight must be [H, W] or [1, H, W] = [%d, %d], got %s" % (who, H, W, tuple(weight.shape)))
+    if weight.dtype != torch.float32:
+        raise TypeError("%s: weight must be float32 weights in [0, 1], got %s" % (who, weight.dtype))
+    if weight.device != device:
+        raise RuntimeError("%s: weight is on %s, the images on %s" % (who, weight.device, device))
+    return weight.detach().reshape(H, W).contiguous()
 
 
-def ssim(img1, img2, window_size=11, size_average=True):
-    """utils/loss_utils.py:37-68 for the arguments AD-GS uses (11x11 window, mean over everything)."""
+def _l1_ssim_weighted_fwd(img, ref, w, maps, out2):
+    """-> (work, token): the backward reads sum w from `work`, so both live with the autograd context."""
+    H, W = img.shape[-2:]
+    work, tok = _work(img.device, L1_SSIM_WEIGHTED_WORK_DOUBLES)
+    if img.numel():
+        _lib.call("adgs_l1_ssim_weighted_forward", img.device, img.numel() // (H * W), H, W, img.data_ptr(), ref.data_ptr(), w.data_ptr(), work.data_ptr(),
+                  *[_ptr(m) for m in maps], out2)
+    tok.done()
+    return work, tok
+
+
+def _l1_ssim_weighted_bwd(img, ref, w, maps, work, g_l1, g_ssim, out):
+    H, W = img.shape[-2:]
+    if img.numel():
+        _lib.call("adgs_l1_ssim_weighted_backward", img.device, img.numel() // (H * W), H, W, img.data_ptr(), ref.data_ptr(), w.data_ptr(),
+                  *[m.data_ptr() for m in maps], work.data_ptr(), g_l1, g_ssim, out)
+
+
+class _L1SSIMWeighted(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, gt, w):
+        img, ref = image.contiguous().float(), gt.contiguous().float()
+        need = ctx.needs_input_grad[0]
+        maps = [torch.empty_like(img) for _ in range(3)] if need else [None] * 3
+        means = _scalar(img.device, img.numel(), 2)
+        work, tok = _l1_ssim_weighted_fwd(img, ref, w, maps, means.data_ptr())
+        if need:
+            ctx.token = tok
+            ctx.save_for_backward(img, ref, w, work, *maps)
+        return means[0], means[1]
+
+    @staticmethod
+    def backward(ctx, g_l1, g_ssim):
+        img, ref, w, work, *maps = ctx.saved_tensors
+        out, gl, gs = torch.empty_like(img), _g1(g_l1), _g1(g_ssim)
+        _l1_ssim_weighted_bwd(img, ref, w, maps, work, _ptr(gl), _ptr(gs), out.data_ptr())
+        return out, None, None
+
+
+def l1_ssim(image, gt, weight=None):
+    """(mean |image - gt|, mean SSIM(image, gt)) -- both differentiable w.r.t. `image`.
+
+    weight: an optional float32 [H, W] or [1, H, W] tensor of supervision weights on the images' device, meant to lie in [0, 1] (not
+    checked); a constant, shared by every channel and every leading dimension of [..., C, H, W].  With P planes and Sw = sum(weight):
+        L1_w = sum_planes sum_pixels w |image - gt| / (P Sw)          SSIM_w = sum_planes sum_pixels w ssim_map / (P Sw)
+    The SSIM map is the unchanged one, computed from the UNMASKED images: the weight applies to the map, not to the images.  This is the
+    region definition of adgs.metrics.Evaluator, so the loss over a region and the evaluation metric over the same region are the same
+    number; the consequence is that pixels within 5 px of a masked area still influence the loss through the 11x11 window.
+    Sw = 0 (decided on the device) gives (0, 0) and an all-zero gradient."""
+    if weight is None:
+        return _L1SSIM.apply(image, gt.detach())
+    if image.dim() < 3 or image.shape != gt.shape:
+        raise ValueError("l1_ssim: image and gt must have the same [..., C, H, W] shape")
+    w = _check_weight(weight, image.shape[-2], image.shape[-1], image.device, "l1_ssim")
+    if not image.is_cuda or not gt.is_cuda:
+        raise RuntimeError("l1_ssim: tensors must be on a HIP device; there is no CPU path")
+    return _L1SSIMWeighted.apply(image, gt.detach(), w)
+
+
+def l1_loss(network_output, gt, weight=None):
+    """utils/loss_utils.py:20-21; `weight`: see l1_ssim."""
+    return l1_ssim(network_output, gt, weight)[0]
+
+
+def ssim(img1, img2, window_size=11, size_average=True, weight=None):
+    """utils/loss_utils.py:37-68 for the arguments AD-GS uses (11x11 window, mean over everything); `weight`: see l1_ssim."""
     if window_size != 11 or not size_average:
         raise NotImplementedError("the HIP ssim implements window_size=11, size_average=True (train.py:80)")
-    return l1_ssim(img1, img2)[1]
+    return l1_ssim(img1, img2, weight)[1]
 
 
-def photometric_loss(image, gt, lambda_dssim, lambda_l1=1.0):
-    """train.py:79-80,112: (1 - lambda_dssim) * lambda_l1 * L1 + lambda_dssim * (1 - SSIM); returns (loss, Ll1, dssim_loss)."""
-    l1, s = l1_ssim(image, gt)
+def photometric_loss(image, gt, lambda_dssim, lambda_l1=1.0, weight=None):
+    """train.py:79-80,112: (1 - lambda_dssim) * lambda_l1 * L1 + lambda_dssim * (1 - SSIM); returns (loss, Ll1, dssim_loss).
+    `weight`: see l1_ssim."""
+    l1, s = l1_ssim(image, gt, weight)
     dssim = 1.0 - s
     return (1.0 - lambda_dssim) * lambda_l1 * l1 + lambda_dssim * dssim, l1, dssim
 
@@ -322,9 +397,50 @@ class _BceClip(torch.autograd.Function):
         return out.reshape(ctx.shape), None, None, None, None, None
 
 
-def bce_clip_loss(pred, target, lo=1e-3, hi=1.0 - 1e-3, invert=False, positive_target=False):
-    """mean BCE(q, t) with q = clip(pred, lo, hi) (1 - clip(...) with `invert`) and t = target ((target > 0) with `positive_target`)."""
-    return _BceClip.apply(pred, target.detach(), lo, hi, invert, positive_target)
+def _bce_weighted_fwd(p, t, w, params, out):
+    """-> (work, token): the backward reads sum w from `work`, so both live with the autograd context."""
+    work, tok = _work(p.device, AUX_WORK_DOUBLES)
+    _lib.call("adgs_bce_clip_weighted_forward", p.device, p.numel(), p.data_ptr(), t.data_ptr(), w.data_ptr(), *params, work.data_ptr(), out)
+    tok.done()
+    return work, tok
+
+
+def _bce_weighted_bwd(p, t, w, params, work, g_loss, out):
+    _lib.call("adgs_bce_clip_weighted_backward", p.device, p.numel(), p.data_ptr(), t.data_ptr(), w.data_ptr(), *params, work.data_ptr(), g_loss, out)
+
+
+class _BceClipWeighted(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, w, lo, hi, invert, positive_target):
+        p, t = pred.contiguous().float(), target.contiguous().float()
+        ctx.params, ctx.shape = (float(lo), float(hi), int(bool(invert)), int(bool(positive_target))), pred.shape
+        out = _scalar(p.device, p.numel())
+        work, ctx.token = _bce_weighted_fwd(p, t, w, ctx.params, out.data_ptr())
+        ctx.save_for_backward(p, t, w, work)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        p, t, w, work = ctx.saved_tensors
+        out, gl = torch.empty_like(p), _g1(g_loss)
+        _bce_weighted_bwd(p, t, w, ctx.params, work, gl.data_ptr(), out.data_ptr())
+        return out.reshape(ctx.shape), None, None, None, None, None, None
+
+
+def bce_clip_loss(pred, target, lo=1e-3, hi=1.0 - 1e-3, invert=False, positive_target=False, weight=None):
+    """mean BCE(q, t) with q = clip(pred, lo, hi) (1 - clip(...) with `invert`) and t = target ((target > 0) with `positive_target`).
+    weight: an optional float32 [H, W] or [1, H, W] tensor over the H x W elements of `pred` ([H, W] or [1, H, W]): sum w bce / sum w,
+    0 with a zero gradient when sum w = 0 (decided on the device)."""
+    if weight is None:
+        return _BceClip.apply(pred, target.detach(), lo, hi, invert, positive_target)
+    if pred.dim() < 2 or pred.numel() != pred.shape[-2] * pred.shape[-1]:
+        raise ValueError("bce_clip_loss: with a weight, pred must be [H, W] or [1, H, W], got %s" % (tuple(pred.shape),))
+    if pred.numel() != target.numel():
+        raise ValueError("bce_clip_loss: prediction and target must have the same number of elements")
+    w = _check_weight(weight, pred.shape[-2], pred.shape[-1], pred.device, "bce_clip_loss")
+    if not pred.is_cuda or not target.is_cuda:
+        raise RuntimeError("bce_clip_loss: tensors must be on a HIP device; there is no CPU path")
+    return _BceClipWeighted.apply(pred, target.detach(), w, lo, hi, invert, positive_target)
 
 
 # (lo, hi, invert, positive_target) of the two BCE terms of a training iteration: obj_loss, sky_loss and the fused _ImageLosses node read these
@@ -332,14 +448,61 @@ OBJ_BCE = (1e-3, 1.0 - 1e-3, 0, 1)
 SKY_BCE = (1e-3, 1.0 - 1e-3, 1, 0)
 
 
-def obj_loss(img_semantic, gt_semantic):
-    """train.py:95-98: binary_cross_entropy(clip(img_semantic, 1e-3, 1 - 1e-3)[0], (gt_semantic > 0).float())."""
-    return bce_clip_loss(img_semantic[0] if img_semantic.dim() == 3 else img_semantic, gt_semantic, *OBJ_BCE)
+def obj_loss(img_semantic, gt_semantic, weight=None):
+    """train.py:95-98: binary_cross_entropy(clip(img_semantic, 1e-3, 1 - 1e-3)[0], (gt_semantic > 0).float()); `weight`: see bce_clip_loss."""
+    return bce_clip_loss(img_semantic[0] if img_semantic.dim() == 3 else img_semantic, gt_semantic, *OBJ_BCE, weight=weight)
 
 
-def sky_loss(img_opacity, gt_sky):
-    """train.py:100-103: binary_cross_entropy(1 - clip(img_opacity, 1e-3, 1 - 1e-3), gt_sky)."""
-    return bce_clip_loss(img_opacity, gt_sky, *SKY_BCE)
+def sky_loss(img_opacity, gt_sky, weight=None):
+    """train.py:100-103: binary_cross_entropy(1 - clip(img_opacity, 1e-3, 1 - 1e-3), gt_sky); `weight`: see bce_clip_loss."""
+    return bce_clip_loss(img_opacity, gt_sky, *SKY_BCE, weight=weight)
+
+
+class _LidarDepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, lidar_depth, lidar_mask, inv_depth):
+        d = depth.contiguous().float()
+        ctx.inv_depth, ctx.shape = int(bool(inv_depth)), depth.shape
+        out = _scalar(d.device, d.numel())
+        work, ctx.token = _work(d.device, AUX_WORK_DOUBLES)
+        if d.numel():
+            _lib.call("adgs_lidar_depth_loss_forward", d.device, d.numel(), d.data_ptr(), lidar_depth.data_ptr(), lidar_mask.data_ptr(), ctx.inv_depth,
+                      work.data_ptr(), out.data_ptr())
+        ctx.token.done()
+        ctx.save_for_backward(d, lidar_depth, lidar_mask, work)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        d, lidar_depth, lidar_mask, work = ctx.saved_tensors
+        out, gl = torch.empty_like(d), _g1(g_loss)
+        if d.numel():
+            _lib.call("adgs_lidar_depth_loss_backward", d.device, d.numel(), d.data_ptr(), lidar_depth.data_ptr(), lidar_mask.data_ptr(), ctx.inv_depth,
+                      work.data_ptr(), gl.data_ptr(), out.data_ptr())
+        return out.reshape(ctx.shape), None, None, None
+
+
+def lidar_depth_loss(depth, lidar_depth, lidar_mask, inv_depth=False):
+    """Sparse metric depth term over the `depth` and `mask` arrays of a lidar_depth/*.npz file (scripts/kitti/kitti.py:185-188,
+    scripts/waymo/waymo.py:329, scripts/nuscene/nuscene.py:90): depth is the rendered [H, W] (or [1, H, W]) depth, a pixel is valid iff
+    lidar_mask > 0 and lidar_depth > 0 (a bool mask is converted), its target is lidar_depth or, with inv_depth=True, 1 / lidar_depth
+    (the rasterizer renders inverse depth under pipe.inv_depth: the caller says which they rendered).
+        loss = sum_valid m |depth - target| / sum_valid m
+    with no scale or shift fitted (get_depth_loss is the scale/shift-invariant monocular term); 0 with a zero gradient when nothing is
+    valid, decided on the device.  One reduction pass and one element-wise backward; differentiable w.r.t. `depth`."""
+    for t, name in ((depth, "depth"), (lidar_depth, "lidar_depth"), (lidar_mask, "lidar_mask")):
+        if not torch.is_tensor(t):
+            raise TypeError("lidar_depth_loss: %s must be a tensor, got %s" % (name, type(t).__name__))
+    if depth.dim() < 2 or depth.numel() != depth.shape[-2] * depth.shape[-1]:
+        raise ValueError("lidar_depth_loss: depth must be [H, W] or [1, H, W], got %s" % (tuple(depth.shape),))
+    if lidar_depth.numel() != depth.numel() or lidar_mask.numel() != depth.numel():
+        raise ValueError("lidar_depth_loss: lidar_depth %s and lidar_mask %s must have the %d elements of depth"
+                         % (tuple(lidar_depth.shape), tuple(lidar_mask.shape), depth.numel()))
+    if lidar_depth.device != depth.device or lidar_mask.device != depth.device:
+        raise RuntimeError("lidar_depth_loss: lidar_depth is on %s and lidar_mask on %s, depth on %s" % (lidar_depth.device, lidar_mask.device, depth.device))
+    if not depth.is_cuda:
+        raise RuntimeError("lidar_depth_loss: tensors must be on a HIP device; there is no CPU path")
+    return _LidarDepthLoss.apply(depth, lidar_depth.detach().contiguous().float(), lidar_mask.detach().contiguous().float(), inv_depth)
 
 
 # ---------------------------------------------------------------- neighbourhood regularisers (train.py:104-113)
@@ -471,10 +634,12 @@ class _ImageLosses(torch.autograd.Function):
     """L1, SSIM, depth loss, flow loss, object BCE, sky BCE -- the `_*_fwd` / `_*_bwd` pairs of the six functions above, in their order, behind
     one autograd node: six Python-level Function calls forward and six backward (each ~30 us of host time around a 5 - 90 us kernel)
     become two, so the short kernels of this section no longer wait for the host between them (tools/iteration_gaps.py: ~100 us of
-    idle GPU per iteration in front of the rasterizer's backward).  Output: a [6] tensor (Ll1, ssim, depth, flow, obj, sky)."""
+    idle GPU per iteration in front of the rasterizer's backward).  Output: a [6] tensor (Ll1, ssim, depth, flow, obj, sky).
+    `w`: the checked supervision weight or None; with one, L1 / SSIM and the two BCE terms are the weighted forms and the depth term takes it
+    as its mask (the flow term's selection is flow_vis)."""
 
     @staticmethod
-    def forward(ctx, image, depth, img_flow, img_opacity, img_semantic, gt_image, gt_depth, flow, flow_vis, cam, dist, gt_semantic, gt_sky):
+    def forward(ctx, image, depth, img_flow, img_opacity, img_semantic, gt_image, gt_depth, flow, flow_vis, cam, dist, gt_semantic, gt_sky, w):
         if not image.is_cuda:
             raise RuntimeError("image_losses: tensors must be on a HIP device; there is no CPU path")
         f32 = lambda t: t.contiguous().float()
@@ -492,28 +657,48 @@ class _ImageLosses(torch.autograd.Function):
         terms = _scalar(img.device, img.numel(), 6)
         maps = [torch.empty_like(img) for _ in range(3)]
         p0 = terms.data_ptr()
-        _l1_ssim_fwd(img, ref, maps, p0)
-        w_depth, tok_depth = _depth_fwd(dep, gdep, None, p0 + 8)
+        if w is None:
+            _l1_ssim_fwd(img, ref, maps, p0)
+            weighted = ()
+        else:
+            w_ssim, tok_ssim = _l1_ssim_weighted_fwd(img, ref, w, maps, p0)
+        w_depth, tok_depth = _depth_fwd(dep, gdep, w, p0 + 8)
         w_flow, tok_flow = _flow_fwd(cam, fl_img, fl, vis, op, float(dist), p0 + 12)
-        _bce_fwd(sem, gsem, OBJ_BCE, p0 + 16)
-        _bce_fwd(op, gsky, SKY_BCE, p0 + 20)
-        ctx.save_for_backward(img, ref, *maps, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky)
-        ctx.tokens, ctx.cam, ctx.dist = (tok_depth, tok_flow), cam, float(dist)
+        if w is None:
+            _bce_fwd(sem, gsem, OBJ_BCE, p0 + 16)
+            _bce_fwd(op, gsky, SKY_BCE, p0 + 20)
+            ctx.tokens = (tok_depth, tok_flow)
+        else:
+            w_obj, tok_obj = _bce_weighted_fwd(sem, gsem, w, OBJ_BCE, p0 + 16)
+            w_sky, tok_sky = _bce_weighted_fwd(op, gsky, w, SKY_BCE, p0 + 20)
+            weighted = (w, w_ssim, w_obj, w_sky)
+            ctx.tokens = (tok_depth, tok_flow, tok_ssim, tok_obj, tok_sky)
+        ctx.save_for_backward(img, ref, *maps, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky, *weighted)
+        ctx.cam, ctx.dist = cam, float(dist)
         ctx.shapes = (image.shape, depth.shape, img_flow.shape, img_opacity.shape, img_semantic.shape)
         return terms
 
     @staticmethod
     def backward(ctx, g):
-        img, ref, d_mu1, d_e11, d_e12, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky = ctx.saved_tensors
+        img, ref, d_mu1, d_e11, d_e12, dep, gdep, w_depth, fl_img, fl, vis, op, w_flow, sem, gsem, gsky, *weighted = ctx.saved_tensors
         g = g.contiguous().float()
         p0 = g.data_ptr()
         g_img, g_dep, g_fl = torch.empty_like(img), torch.empty_like(dep), torch.empty_like(fl_img)
         g_op, g_op2, g_sem = torch.empty_like(op), torch.empty_like(op), torch.empty_like(sem)
-        _l1_ssim_bwd(img, ref, (d_mu1, d_e11, d_e12), p0, p0 + 4, g_img.data_ptr())
-        _depth_bwd(dep, gdep, None, w_depth, p0 + 8, g_dep.data_ptr())
+        if weighted:
+            w, w_ssim, w_obj, w_sky = weighted
+            _l1_ssim_weighted_bwd(img, ref, w, (d_mu1, d_e11, d_e12), w_ssim, p0, p0 + 4, g_img.data_ptr())
+        else:
+            w = None
+            _l1_ssim_bwd(img, ref, (d_mu1, d_e11, d_e12), p0, p0 + 4, g_img.data_ptr())
+        _depth_bwd(dep, gdep, w, w_depth, p0 + 8, g_dep.data_ptr())
         _flow_bwd(ctx.cam, fl_img, fl, vis, op, ctx.dist, w_flow, p0 + 12, g_fl.data_ptr(), g_op.data_ptr())
-        _bce_bwd(sem, gsem, OBJ_BCE, p0 + 16, g_sem.data_ptr())
-        _bce_bwd(op, gsky, SKY_BCE, p0 + 20, g_op2.data_ptr())
+        if weighted:
+            _bce_weighted_bwd(sem, gsem, w, OBJ_BCE, w_obj, p0 + 16, g_sem.data_ptr())
+            _bce_weighted_bwd(op, gsky, w, SKY_BCE, w_sky, p0 + 20, g_op2.data_ptr())
+        else:
+            _bce_bwd(sem, gsem, OBJ_BCE, p0 + 16, g_sem.data_ptr())
+            _bce_bwd(op, gsky, SKY_BCE, p0 + 20, g_op2.data_ptr())
         g_op.add_(g_op2)                               # img_opacity feeds the flow loss and the sky loss
         s_img, s_dep, s_fl, s_op, s_sem = ctx.shapes
         if len(s_sem) == 3 and s_sem[0] > 1:           # [D_S, H, W]: only channel 0 enters the object loss (train.py:95-98)
@@ -521,15 +706,19 @@ class _ImageLosses(torch.autograd.Function):
             g_sem_out[0].copy_(g_sem)
         else:
             g_sem_out = g_sem.reshape(s_sem)
-        return (g_img.reshape(s_img), g_dep.reshape(s_dep), g_fl.reshape(s_fl), g_op.reshape(s_op), g_sem_out) + (None,) * 8
+        return (g_img.reshape(s_img), g_dep.reshape(s_dep), g_fl.reshape(s_fl), g_op.reshape(s_op), g_sem_out) + (None,) * 9
 
 
-def image_losses(image, gt_image, depth, gt_depth, img_flow, flow_pkg, img_opacity, img_semantic, gt_semantic, gt_sky, dist=1e-3):
+def image_losses(image, gt_image, depth, gt_depth, img_flow, flow_pkg, img_opacity, img_semantic, gt_semantic, gt_sky, dist=1e-3, weight=None):
     """The six image terms of a training iteration in one autograd node: returns (Ll1, ssim, depth_loss, flow_loss, obj_loss, sky_loss) --
     bit for bit what l1_ssim, get_depth_loss (no mask), get_flow_loss, obj_loss and sky_loss return for the same arguments
-    (utils/loss_utils.py:20-106, train.py:78-99; flow_pkg = (_, K, R, T, flow, flow_vis) as in train.py:68-71)."""
+    (utils/loss_utils.py:20-106, train.py:78-99; flow_pkg = (_, K, R, T, flow, flow_vis) as in train.py:68-71).
+    weight: an optional supervision weight (see l1_ssim).  With one the node returns what l1_ssim(..., weight), get_depth_loss(..., mask=weight),
+    get_flow_loss, obj_loss(..., weight) and sky_loss(..., weight) return.  The flow term is unchanged: its selection comes from flow_vis,
+    so fold the mask into it once at load time (`flow_vis * (weight > 0.5)`)."""
     _, K, R, T, flow, flow_vis = flow_pkg
+    w = None if weight is None else _check_weight(weight, image.shape[-2], image.shape[-1], image.device, "image_losses")
     cam = _FlowCam(K, R, T, image.device)
     terms = _ImageLosses.apply(image, depth, img_flow, img_opacity, img_semantic, gt_image.detach(), gt_depth.detach(), flow.detach(), flow_vis.detach(),
-                               cam, float(dist), gt_semantic.detach(), gt_sky.detach())
+                               cam, float(dist), gt_semantic.detach(), gt_sky.detach(), w)
     return tuple(terms.unbind(0))

@@ -16,14 +16,38 @@ namespace {
 
 using namespace ssimwin;                  // tile geometry, Window, stage_halos, load_run, window4: shared with metrics.hip
 
-__global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, Window win,
-	double* __restrict__ sums, float* __restrict__ d_mu1, float* __restrict__ d_e11, float* __restrict__ d_e12) {
+// WEIGHTED: a per-pixel supervision weight w [H, W], shared by every plane, applies to the MAP and to |image - gt| (the images enter the
+// windows unweighted: the region definition of metrics.hip).  The thread reads w at its two output pixels only; the sums are
+// (sum w |d|, sum w ssim, sum w) with sum w counted by the workgroups of plane 0 alone, and the three maps are stored times w, so the
+// backward's convolutions are those of the unweighted form.  A workgroup whose whole tile has w = 0 (an ego-vehicle mask is whole rows of
+// them) writes zero maps and skips the staging and the windows.
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, const float* __restrict__ weight,
+	Window win, double* __restrict__ sums, float* __restrict__ d_mu1, float* __restrict__ d_e11, float* __restrict__ d_e12) {
+	constexpr int NS = WEIGHTED ? 3 : 2;
 	__shared__ __attribute__((aligned(16))) float s1[HSY][SSTR], s2[HSY][SSTR];
 	__shared__ __attribute__((aligned(16))) float h[5][HSY][HSTR];      // horizontally filtered x1, x2, x1^2, x2^2, x1 x2
-	__shared__ double red[2][LT / WAVE];
+	__shared__ double red[NS][LT / WAVE];
 	const int tid = threadIdx.x;
 	const int x0 = blockIdx.x * TSX, y0 = blockIdx.y * TSY;
 	const size_t plane = (size_t)blockIdx.z * H * W;
+	float wv[2] = { 1.f, 1.f };
+	if constexpr (WEIGHTED) {
+		const int gx = x0 + (tid & (TSX - 1)), gy = y0 + 2 * (tid >> 5);
+#pragma unroll
+		for (int o = 0; o < 2; o++) wv[o] = (gx < W && gy + o < H) ? weight[(size_t)(gy + o) * W + gx] : 0.f;
+		if (!__syncthreads_or(wv[0] != 0.f || wv[1] != 0.f)) {
+			if (d_mu1 && gx < W) {
+#pragma unroll
+				for (int o = 0; o < 2; o++) {
+					if (gy + o >= H) continue;
+					const size_t oo = plane + (size_t)(gy + o) * W + gx;
+					d_mu1[oo] = 0.f; d_e11[oo] = 0.f; d_e12[oo] = 0.f;
+				}
+			}
+			return;
+		}
+	}
 	{
 		float (*const dst[2])[SSTR] = { s1, s2 };
 		const float* const src[2] = { img, gt };
@@ -65,7 +89,7 @@ __global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const flo
 			acc[q][o] = a;
 		}
 	}
-	double l1 = 0.0, sm = 0.0;
+	double l1 = 0.0, sm = 0.0, sw = 0.0;
 #pragma unroll
 	for (int o = 0; o < 2; o++) {
 		const int ty = 2 * g + o, gx = x0 + tx, gy = y0 + ty;
@@ -75,33 +99,49 @@ __global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const flo
 		const float sg1 = e11 - mu1_sq, sg2 = e22 - mu2_sq, sg12 = e12 - mu12;
 		const float A1 = 2.f * mu12 + C1, A2 = 2.f * sg12 + C2, B1 = mu1_sq + mu2_sq + C1, B2 = sg1 + sg2 + C2;
 		const float D = B1 * B2, inv = 1.f / D;
-		sm += (double)((A1 * A2) * inv);
-		l1 += (double)fabsf(s1[ty + WR][tx + WR] - s2[ty + WR][tx + WR]);
+		double map = (double)((A1 * A2) * inv), ad = (double)fabsf(s1[ty + WR][tx + WR] - s2[ty + WR][tx + WR]);
+		if constexpr (WEIGHTED) {
+			map *= (double)wv[o]; ad *= (double)wv[o];
+			if (blockIdx.z == 0) sw += (double)wv[o];
+		}
+		sm += map;
+		l1 += ad;
 		if (d_mu1) {
 			const size_t oo = plane + (size_t)gy * W + gx;
 			// partial derivatives of the map w.r.t. the window means mu1, E[x1^2], E[x1 x2] (mu2, E[x2^2] belong to gt)
 			const float num = A1 * A2;
 			const float dnum = 2.f * mu2 * A2 - 2.f * mu2 * A1;           // dA1 = 2 mu2, dA2 = -2 mu2
 			const float dden = 2.f * mu1 * B2 - 2.f * mu1 * B1;           // dB1 = 2 mu1, dB2 = -2 mu1
-			d_mu1[oo] = (dnum * D - num * dden) * (inv * inv);
-			d_e11[oo] = -num * inv / B2;                                  // dB2 = 1
-			d_e12[oo] = 2.f * A1 * inv;                                   // dA2 = 2
+			float p_mu1 = (dnum * D - num * dden) * (inv * inv);
+			float p_e11 = -num * inv / B2;                                // dB2 = 1
+			float p_e12 = 2.f * A1 * inv;                                 // dA2 = 2
+			if constexpr (WEIGHTED) { p_mu1 *= wv[o]; p_e11 *= wv[o]; p_e12 *= wv[o]; }
+			d_mu1[oo] = p_mu1; d_e11[oo] = p_e11; d_e12[oo] = p_e12;
 		}
 	}
 #pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) { l1 += __shfl_xor(l1, off, WAVE); sm += __shfl_xor(sm, off, WAVE); }
-	if ((tid & (WAVE - 1)) == 0) { red[0][tid / WAVE] = l1; red[1][tid / WAVE] = sm; }
+	for (int off = WAVE / 2; off > 0; off >>= 1) {
+		l1 += __shfl_xor(l1, off, WAVE); sm += __shfl_xor(sm, off, WAVE);
+		if constexpr (WEIGHTED) sw += __shfl_xor(sw, off, WAVE);
+	}
+	if ((tid & (WAVE - 1)) == 0) {
+		red[0][tid / WAVE] = l1; red[1][tid / WAVE] = sm;
+		if constexpr (WEIGHTED) red[2][tid / WAVE] = sw;
+	}
 	__syncthreads();
-	if (tid < 2) {
+	if (tid < NS) {
 		double t = 0.0;
 		for (int w = 0; w < LT / WAVE; w++) t += red[tid][w];
 		const unsigned b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-		atomicAdd(sums + 2 * (b % ADGS_LOSS_SLOTS) + tid, t);
+		atomicAdd(sums + NS * (b % ADGS_LOSS_SLOTS) + tid, t);
 	}
 }
 
-__global__ void __launch_bounds__(LT) l1_ssim_bwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, Window win,
-	const float* __restrict__ d_mu1, const float* __restrict__ d_e11, const float* __restrict__ d_e12,
+// WEIGHTED: the maps arrive times w (see the forward), the L1 term takes w at the pixel, and 1 / (planes sum w) replaces inv_n: sum w is
+// read from the totals the forward's finish kernel left in the work buffer (0 -> an all-zero gradient).
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(LT) l1_ssim_bwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, const float* __restrict__ weight,
+	const double* __restrict__ totals, Window win, const float* __restrict__ d_mu1, const float* __restrict__ d_e11, const float* __restrict__ d_e12,
 	const float* __restrict__ g_l1, const float* __restrict__ g_ssim, float inv_n, float* __restrict__ out) {
 	__shared__ __attribute__((aligned(16))) float s[3][HSY][SSTR];
 	__shared__ __attribute__((aligned(16))) float h[3][HSY][HSTR];
@@ -143,6 +183,10 @@ __global__ void __launch_bounds__(LT) l1_ssim_bwd_kernel(int H, int W, const flo
 		}
 	}
 	const float gs = g_ssim ? g_ssim[0] : 0.f, gl = g_l1 ? g_l1[0] : 0.f;
+	if constexpr (WEIGHTED) {
+		const double sw = totals[2];
+		inv_n = sw > 0.0 ? (float)(1.0 / ((double)gridDim.z * sw)) : 0.f;
+	}
 #pragma unroll
 	for (int o = 0; o < 2; o++) {
 		const int gx = x0 + tx, gy = y0 + 2 * g + o;
@@ -150,7 +194,8 @@ __global__ void __launch_bounds__(LT) l1_ssim_bwd_kernel(int H, int W, const flo
 		const size_t oo = plane + (size_t)gy * W + gx;
 		const float x1 = img[oo], x2 = gt[oo];
 		const float dx = x1 - x2;
-		const float sgn = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f);             // torch.abs backward: sign(), 0 at 0
+		float sgn = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f);                   // torch.abs backward: sign(), 0 at 0
+		if constexpr (WEIGHTED) sgn *= weight[(size_t)gy * W + gx];
 		out[oo] = gl * sgn * inv_n + gs * inv_n * (acc[0][o] + 2.f * x1 * acc[1][o] + x2 * acc[2][o]);
 	}
 }
@@ -360,15 +405,26 @@ __global__ void __launch_bounds__(256) flow_loss_bwd_kernel(int H, int W, const 
 
 // mean BCE of q = clip(pred, lo, hi) (or 1 - clip) against t = target (or target > 0): train.py:95-103
 __device__ __forceinline__ float bce_target(float t, int positive) { return positive ? (t > 0.f ? 1.f : 0.f) : t; }
+__device__ __forceinline__ float bce_value(float pred, float target, float lo, float hi, int invert, int positive) {
+	const float c = fminf(fmaxf(pred, lo), hi);
+	const float q = invert ? 1.0f - c : c;
+	const float t = bce_target(target, positive);
+	return -(t * fmaxf(logf(q), -100.f) + (1.f - t) * fmaxf(logf(1.f - q), -100.f));     // torch clamps the logs at -100
+}
+// d BCE / d pred: (q - t) / (q (1 - q)) with torch's eps-clamped denominator; clamp passes the gradient on [lo, hi]
+__device__ __forceinline__ float bce_dpred(float x, float target, float lo, float hi, int invert, int positive, bool& inside) {
+	const float c = fminf(fmaxf(x, lo), hi);
+	const float q = invert ? 1.0f - c : c;
+	const float t = bce_target(target, positive);
+	const float dq = (q - t) / fmaxf(q * (1.f - q), 1e-12f);
+	inside = x >= lo && x <= hi;
+	return invert ? -dq : dq;
+}
 __global__ void __launch_bounds__(256) bce_clip_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target, float lo, float hi,
 	int invert, int positive, double* __restrict__ work) {
 	double sum = 0;
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-		const float c = fminf(fmaxf(pred[i], lo), hi);
-		const float q = invert ? 1.0f - c : c;
-		const float t = bce_target(target[i], positive);
-		sum += (double)(-(t * fmaxf(logf(q), -100.f) + (1.f - t) * fmaxf(logf(1.f - q), -100.f)));     // torch clamps the logs at -100
-	}
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+		sum += (double)bce_value(pred[i], target[i], lo, hi, invert, positive);
 #pragma unroll
 	for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
 	if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2, sum);
@@ -378,14 +434,70 @@ __global__ void __launch_bounds__(256) bce_clip_bwd_kernel(int n, const float* _
 	int invert, int positive, const float* __restrict__ g_loss, float* __restrict__ out) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const float x = pred[i];
-	const float c = fminf(fmaxf(x, lo), hi);
-	const float q = invert ? 1.0f - c : c;
-	const float t = bce_target(target[i], positive);
-	// d BCE / dq = (q - t) / (q (1 - q)) with torch's eps-clamped denominator; clamp passes the gradient on [lo, hi]
-	const float dq = (q - t) / fmaxf(q * (1.f - q), 1e-12f);
-	const bool inside = x >= lo && x <= hi;
-	out[i] = inside ? g_loss[0] * (invert ? -dq : dq) / (float)n : 0.f;
+	bool inside;
+	const float d = bce_dpred(pred[i], target[i], lo, hi, invert, positive, inside);
+	out[i] = inside ? g_loss[0] * d / (float)n : 0.f;
+}
+// the same with a per-element weight: sum w bce / sum w; the finish kernel's "count" is sum w, which the backward reads from the work buffer
+__device__ __forceinline__ void aux_add2(double sum, double cnt, double* __restrict__ work) {
+#pragma unroll
+	for (int off = WAVE / 2; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, WAVE); cnt += __shfl_xor(cnt, off, WAVE); }
+	if ((threadIdx.x & (WAVE - 1)) == 0) {
+		const size_t slot = (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2;
+		atomicAdd(work + slot, sum); atomicAdd(work + slot + 1, cnt);
+	}
+}
+__global__ void __launch_bounds__(256) bce_clip_weighted_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target,
+	const float* __restrict__ weight, float lo, float hi, int invert, int positive, double* __restrict__ work) {
+	double sum = 0, cnt = 0;
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+		const float w = weight[i];
+		sum += (double)w * (double)bce_value(pred[i], target[i], lo, hi, invert, positive);
+		cnt += (double)w;
+	}
+	aux_add2(sum, cnt, work);
+}
+__global__ void __launch_bounds__(256) bce_clip_weighted_bwd_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target,
+	const float* __restrict__ weight, float lo, float hi, int invert, int positive, const double* __restrict__ work, const float* __restrict__ g_loss,
+	float* __restrict__ out) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const double sw = work[2 * AUX_SLOTS + 1];
+	bool inside;
+	const float d = bce_dpred(pred[i], target[i], lo, hi, invert, positive, inside);
+	out[i] = inside && sw > 0.0 ? g_loss[0] * weight[i] * d * (float)(1.0 / sw) : 0.f;
+}
+
+// ---------------------------------------------------------------- sparse metric depth (the lidar_depth/*.npz arrays of the preparation scripts)
+// sum m |depth - target| / sum m over the pixels with m > 0 and lidar > 0; target = lidar, or 1 / lidar when inverse depth was rendered.
+// No scale or shift is fitted.  Same aux work layout: (sum, sum m).
+// the target and the residual in double: 1 / lidar next to a rendered inverse depth is a difference of close numbers
+__device__ __forceinline__ bool lidar_residual(float depth, float lidar, float m, int inv_depth, double& r) {
+	if (!(m > 0.f && lidar > 0.f)) return false;
+	r = (double)depth - (inv_depth ? 1.0 / (double)lidar : (double)lidar);
+	return true;
+}
+__global__ void __launch_bounds__(256) lidar_depth_sum_kernel(int n, const float* __restrict__ depth, const float* __restrict__ lidar, const float* __restrict__ mask,
+	int inv_depth, double* __restrict__ work) {
+	double sum = 0, cnt = 0;
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+		const float m = mask[i];
+		double r;
+		if (lidar_residual(depth[i], lidar[i], m, inv_depth, r)) { sum += (double)m * fabs(r); cnt += (double)m; }
+	}
+	aux_add2(sum, cnt, work);
+}
+__global__ void __launch_bounds__(256) lidar_depth_bwd_kernel(int n, const float* __restrict__ depth, const float* __restrict__ lidar, const float* __restrict__ mask,
+	int inv_depth, const double* __restrict__ work, const float* __restrict__ g_loss, float* __restrict__ out) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const double sm = work[2 * AUX_SLOTS + 1];
+	const float m = mask[i];
+	double r;
+	float g = 0.f;
+	if (lidar_residual(depth[i], lidar[i], m, inv_depth, r) && sm > 0.0)
+		g = g_loss[0] * m * (r > 0.0 ? 1.f : (r < 0.0 ? -1.f : 0.f)) * (float)(1.0 / sm);
+	out[i] = g;
 }
 
 } // namespace
@@ -490,7 +602,7 @@ extern "C" int adgs_l1_ssim_forward(int planes, int H, int W, const float* image
 	if (planes > 65535) { set_error("adgs_l1_ssim_forward: more than 65535 planes"); return -1; }
 	static const Window win = make_window();
 	const dim3 grid((W + TSX - 1) / TSX, (H + TSY - 1) / TSY, planes);
-	hipLaunchKernelGGL(l1_ssim_fwd_kernel, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, win, sums, d_mu1, d_e11, d_e12);
+	hipLaunchKernelGGL(l1_ssim_fwd_kernel<false>, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, (const float*)nullptr, win, sums, d_mu1, d_e11, d_e12);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -528,7 +640,95 @@ extern "C" int adgs_l1_ssim_backward(int planes, int H, int W, const float* imag
 	static const Window win = make_window();
 	const dim3 grid((W + TSX - 1) / TSX, (H + TSY - 1) / TSY, planes);
 	const float inv_n = (float)(1.0 / ((double)planes * H * W));
-	hipLaunchKernelGGL(l1_ssim_bwd_kernel, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, win, d_mu1, d_e11, d_e12, g_l1, g_ssim, inv_n, dL_dimage);
+	hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, (const float*)nullptr, (const double*)nullptr, win, d_mu1, d_e11, d_e12,
+		g_l1, g_ssim, inv_n, dL_dimage);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+
+// ---------------------------------------------------------------- the weighted forms (include/adgs_loss.h)
+namespace {
+// totals of the three sums -> work[3 * SLOTS ..] = (sum w |d|, sum w ssim, sum w); out2 = the first two over planes * sum w, 0 when sum w = 0
+__global__ void __launch_bounds__(256) l1_ssim_weighted_finish_kernel(double* __restrict__ work, double planes, float* __restrict__ out2) {
+	__shared__ double s[3][256 / WAVE];
+	double v[3];
+#pragma unroll
+	for (int q = 0; q < 3; q++) {
+		v[q] = work[(size_t)threadIdx.x * 3 + q];
+		work[(size_t)threadIdx.x * 3 + q] = 0.0;                       // consumed
+#pragma unroll
+		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
+		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		double* tot = work + 3 * ADGS_LOSS_SLOTS;
+		for (int q = 0; q < 3; q++) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[q][w]; tot[q] = t; }
+		const double n = planes * tot[2];
+		out2[0] = tot[2] > 0 ? (float)(tot[0] / n) : 0.f; out2[1] = tot[2] > 0 ? (float)(tot[1] / n) : 0.f;
+	}
+}
+}
+extern "C" int adgs_l1_ssim_weighted_forward(int planes, int H, int W, const float* image, const float* gt, const float* weight, double* work,
+	float* d_mu1, float* d_e11, float* d_e12, float* out2, void* stream) {
+	if (planes <= 0 || H <= 0 || W <= 0) return 0;
+	if (!image || !gt || !weight || !work || !out2) { set_error("adgs_l1_ssim_weighted_forward: NULL image / gt / weight / work / out2"); return -1; }
+	if ((d_mu1 != nullptr) != (d_e11 != nullptr) || (d_mu1 != nullptr) != (d_e12 != nullptr)) { set_error("adgs_l1_ssim_weighted_forward: pass all three derivative maps or none"); return -1; }
+	if (planes > 65535) { set_error("adgs_l1_ssim_weighted_forward: more than 65535 planes"); return -1; }
+	static_assert(ADGS_LOSS_SLOTS == 256 && ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES >= 3 * ADGS_LOSS_SLOTS + 3, "one thread per slot row; three totals behind the rows");
+	static const Window win = make_window();
+	const dim3 grid((W + TSX - 1) / TSX, (H + TSY - 1) / TSY, planes);
+	hipLaunchKernelGGL(l1_ssim_fwd_kernel<true>, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, weight, win, work, d_mu1, d_e11, d_e12);
+	hipLaunchKernelGGL(l1_ssim_weighted_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, (double)planes, out2);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+extern "C" int adgs_l1_ssim_weighted_backward(int planes, int H, int W, const float* image, const float* gt, const float* weight,
+	const float* d_mu1, const float* d_e11, const float* d_e12, const double* work, const float* g_l1, const float* g_ssim, float* dL_dimage, void* stream) {
+	if (planes <= 0 || H <= 0 || W <= 0) return 0;
+	if (!image || !gt || !weight || !d_mu1 || !d_e11 || !d_e12 || !work || !dL_dimage) { set_error("adgs_l1_ssim_weighted_backward: NULL pointer"); return -1; }
+	if (planes > 65535) { set_error("adgs_l1_ssim_weighted_backward: more than 65535 planes"); return -1; }
+	static const Window win = make_window();
+	const dim3 grid((W + TSX - 1) / TSX, (H + TSY - 1) / TSY, planes);
+	hipLaunchKernelGGL(l1_ssim_bwd_kernel<true>, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, weight, work + 3 * ADGS_LOSS_SLOTS, win, d_mu1, d_e11, d_e12,
+		g_l1, g_ssim, 0.f, dL_dimage);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+extern "C" int adgs_bce_clip_weighted_forward(int n, const float* pred, const float* target, const float* weight, float lo, float hi, int invert, int positive_target,
+	double* work, float* loss, void* stream_) {
+	if (n <= 0) return 0;
+	if (!pred || !target || !weight || !work || !loss) { set_error("adgs_bce_clip_weighted_forward: NULL pointer"); return -1; }
+	hipStream_t stream = (hipStream_t)stream_;
+	hipLaunchKernelGGL(bce_clip_weighted_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, n, pred, target, weight, lo, hi, invert, positive_target, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+extern "C" int adgs_bce_clip_weighted_backward(int n, const float* pred, const float* target, const float* weight, float lo, float hi, int invert, int positive_target,
+	const double* work, const float* g_loss, float* dL_dpred, void* stream_) {
+	if (n <= 0) return 0;
+	if (!pred || !target || !weight || !work || !g_loss || !dL_dpred) { set_error("adgs_bce_clip_weighted_backward: NULL pointer"); return -1; }
+	hipLaunchKernelGGL(bce_clip_weighted_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream_, n, pred, target, weight, lo, hi, invert, positive_target,
+		work, g_loss, dL_dpred);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+extern "C" int adgs_lidar_depth_loss_forward(int n, const float* depth, const float* lidar_depth, const float* lidar_mask, int inv_depth, double* work, float* loss,
+	void* stream_) {
+	if (n <= 0) return 0;
+	if (!depth || !lidar_depth || !lidar_mask || !work || !loss) { set_error("adgs_lidar_depth_loss_forward: NULL pointer"); return -1; }
+	hipStream_t stream = (hipStream_t)stream_;
+	hipLaunchKernelGGL(lidar_depth_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, n, depth, lidar_depth, lidar_mask, inv_depth, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+extern "C" int adgs_lidar_depth_loss_backward(int n, const float* depth, const float* lidar_depth, const float* lidar_mask, int inv_depth, const double* work,
+	const float* g_loss, float* dL_ddepth, void* stream_) {
+	if (n <= 0) return 0;
+	if (!depth || !lidar_depth || !lidar_mask || !work || !g_loss || !dL_ddepth) { set_error("adgs_lidar_depth_loss_backward: NULL pointer"); return -1; }
+	hipLaunchKernelGGL(lidar_depth_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream_, n, depth, lidar_depth, lidar_mask, inv_depth, work, g_loss, dL_ddepth);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

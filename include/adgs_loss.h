@@ -39,6 +39,23 @@ int adgs_l1_ssim_backward(int planes, int H, int W, const float* image, const fl
 	const float* d_mu1, const float* d_e11, const float* d_e12, const float* g_l1, const float* g_ssim, float* dL_dimage, void* stream);
 
 /*
+ * The same pair with a per-pixel supervision weight: weight is H*W floats (meant to lie in [0, 1]; not checked), shared by every plane.
+ *   out2[0] = sum_planes sum_pixels w |image - gt| / (planes * sum w)      out2[1] = sum_planes sum_pixels w ssim_map / (planes * sum w)
+ * ssim_map is the map of adgs_l1_ssim_forward, computed from the UNWEIGHTED images: the weight applies to the map (the region
+ * definition of include/adgs_metrics.h), so pixels within 5 px of a masked area still influence the loss through the window.
+ * sum w = 0 is decided on the device: out2 = (0, 0) and the backward writes zeros.
+ * work: ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES device doubles: ADGS_LOSS_SLOTS x 3 slot rows (sum w |d|, sum w ssim, sum w; zero on entry and
+ * on return: the forward contains its finish kernel), then the three totals, which the backward reads -- keep the buffer until then.
+ * d_mu1 / d_e11 / d_e12 receive the partial derivatives times w (all NULL for a forward without backward).
+ */
+#define ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES (256 * 3 + 4)
+int adgs_l1_ssim_weighted_forward(int planes, int H, int W, const float* image, const float* gt, const float* weight, double* work,
+	float* d_mu1, float* d_e11, float* d_e12, float* out2, void* stream);
+/* dL_dimage = (g_l1[0] * w * sign(image - gt) + g_ssim[0] * d(sum w ssim_map)/d(image)) / (planes * sum w); all zeros when sum w = 0. */
+int adgs_l1_ssim_weighted_backward(int planes, int H, int W, const float* image, const float* gt, const float* weight,
+	const float* d_mu1, const float* d_e11, const float* d_e12, const double* work, const float* g_l1, const float* g_ssim, float* dL_dimage, void* stream);
+
+/*
  * Scale-and-shift-invariant depth loss: utils/loss_utils.py:70-75 get_depth_loss over
  * utils/depth_utils.py:3-45 (closed-form least squares for scale s and shift t of the prediction, then
  * sum(|s p + t - g| m) / sum(m)), differentiable through s and t like the reference's autograd, with the
@@ -86,6 +103,24 @@ int adgs_bce_clip_forward(int n, const float* pred, const float* target, float l
 	double* work, float* loss, void* stream);
 int adgs_bce_clip_backward(int n, const float* pred, const float* target, float lo, float hi, int invert, int positive_target,
 	const float* g_loss, float* dL_dpred, void* stream);
+
+/* The same term with a weight per element: sum w bce / sum w, 0 (and a zero gradient) when sum w = 0.  work: ADGS_AUX_WORK_DOUBLES,
+ * kept for the backward, which reads sum w from it. */
+int adgs_bce_clip_weighted_forward(int n, const float* pred, const float* target, const float* weight, float lo, float hi, int invert, int positive_target,
+	double* work, float* loss, void* stream);
+int adgs_bce_clip_weighted_backward(int n, const float* pred, const float* target, const float* weight, float lo, float hi, int invert, int positive_target,
+	const double* work, const float* g_loss, float* dL_dpred, void* stream);
+
+/*
+ * Sparse metric depth term over the `depth` and `mask` arrays of a lidar_depth npz file (n = H*W floats each).  A pixel is valid iff
+ * lidar_mask > 0 and lidar_depth > 0; its target is lidar_depth or, with inv_depth, 1 / lidar_depth (what the rasterizer renders under
+ * pipe.inv_depth).  loss = sum_valid m |depth - target| / sum_valid m, no scale or shift fitted; 0 with a zero gradient when nothing is valid.
+ * work: ADGS_AUX_WORK_DOUBLES, kept for the backward (it reads sum m).
+ */
+int adgs_lidar_depth_loss_forward(int n, const float* depth, const float* lidar_depth, const float* lidar_mask, int inv_depth, double* work, float* loss,
+	void* stream);
+int adgs_lidar_depth_loss_backward(int n, const float* depth, const float* lidar_depth, const float* lidar_mask, int inv_depth, const double* work,
+	const float* g_loss, float* dL_ddepth, void* stream);
 
 /*
  * Neighbourhood regularisers of the training loop (train.py:104-113), over GaussianModel.obj_near_idx [G, K] (int64 rows of
