@@ -138,6 +138,10 @@ SIGNATURES = {
     # include/adgs_metrics.h
     "adgs_metrics_work_doubles": (ctypes.c_size_t, [c_i]),
     "adgs_metrics_accumulate": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    # include/adgs_colorcorrect.h
+    "adgs_cc_work_doubles": (ctypes.c_size_t, []),
+    "adgs_cc_fit": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_cc_apply": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

@@ -1437,6 +1437,7 @@ extern "C" int adgs_knn_dist2(int P, const float* points, float* meanDists, char
 #include "../../include/adgs_testing.h"
 #include "../../include/adgs_optim.h"
 #include "../../include/adgs_metrics.h"
+#include "../../include/adgs_colorcorrect.h"
 // the image state of a v2 forward, carved the way that forward carved it
 namespace {
 struct V2ImageView { ImgStateV2 img; size_t wtiles, ncells; };
@@ -1509,7 +1510,7 @@ extern "C" long long adgs_test_v2_scanned_candidates(const char* img_buffer, int
 }
 // sizeof of the structs that cross the ABI by pointer: lets a binding check its mirror (which: 0 adgs_sh_source, 1 adgs_sh_grads,
 // 2 adgs_frame_stats, 3 adgs_frame_status, 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam, 7 adgs_raster_options, 8 adgs_adam_rows,
-// 9 adgs_raster_backward_options, 10 adgs_metrics_desc)
+// 9 adgs_raster_backward_options, 10 adgs_metrics_desc, 11 adgs_cc_desc)
 extern "C" unsigned long long adgs_test_env_reads(void) { return g_env_reads.load(); }
 extern "C" size_t adgs_test_abi_sizeof(int which) {
 	switch (which) {
@@ -1524,6 +1525,7 @@ extern "C" size_t adgs_test_abi_sizeof(int which) {
 	case 8: return sizeof(adgs_adam_rows);
 	case 9: return sizeof(adgs_raster_backward_options);
 	case 10: return sizeof(adgs_metrics_desc);
+	case 11: return sizeof(adgs_cc_desc);
 	default: return 0;
 	}
 }
