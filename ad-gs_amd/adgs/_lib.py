@@ -102,6 +102,8 @@ SIGNATURES = {
     "adgs_bce_clip_weighted_backward": (c_i, [c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
     "adgs_lidar_depth_loss_forward": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "adgs_lidar_depth_loss_backward": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
+    "adgs_depth_smooth_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
+    "adgs_depth_smooth_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     "adgs_group_var_forward": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_group_var_backward": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "adgs_sigma_loss_forward": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p]),

@@ -8,6 +8,7 @@ There is no CPU fallback.
 
 Every image term takes an optional per-pixel supervision weight (`weight=`: ego vehicle, invalid borders of undistorted images, excluded
 regions) -- see l1_ssim -- and `lidar_depth_loss` is the sparse metric depth term over the lidar_depth/*.npz arrays.
+`depth_smoothness_loss` is the edge-aware smoothness prior (first or second order) on the rendered inverse depth.
 """
 import ctypes
 import threading
@@ -503,6 +504,79 @@ def lidar_depth_loss(depth, lidar_depth, lidar_mask, inv_depth=False):
     if not depth.is_cuda:
         raise RuntimeError("lidar_depth_loss: tensors must be on a HIP device; there is no CPU path")
     return _LidarDepthLoss.apply(depth, lidar_depth.detach().contiguous().float(), lidar_mask.detach().contiguous().float(), inv_depth)
+
+
+SMOOTH_WORK_DOUBLES = 256 * 8 + 8        # ADGS_SMOOTH_WORK_DOUBLES
+
+
+class _DepthSmooth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, guide, w, order, normalize, gamma):
+        d = depth.contiguous().reshape(depth.shape[-2:])
+        H, W = d.shape
+        ctx.args = (H, W, 0 if guide is None else guide.shape[0]), (order, normalize, gamma)
+        ctx.shape, ctx.has = depth.shape, (guide is not None, w is not None)
+        out = _scalar(d.device, d.numel())
+        work, ctx.token = _work(d.device, SMOOTH_WORK_DOUBLES)        # the backward reads the totals, s and L from `work`
+        if d.numel():
+            _lib.call("adgs_depth_smooth_forward", d.device, *ctx.args[0], d.data_ptr(), _ptr(guide), _ptr(w), *ctx.args[1], work.data_ptr(), out.data_ptr())
+        ctx.token.done()
+        ctx.save_for_backward(d, work, *[t for t in (guide, w) if t is not None])
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        d, work, *rest = ctx.saved_tensors
+        guide = rest.pop(0) if ctx.has[0] else None
+        w = rest.pop(0) if ctx.has[1] else None
+        out, gl = torch.empty_like(d), _g1(g_loss)
+        if d.numel():
+            _lib.call("adgs_depth_smooth_backward", d.device, *ctx.args[0], d.data_ptr(), _ptr(guide), _ptr(w), *ctx.args[1], work.data_ptr(), gl.data_ptr(), out.data_ptr())
+        return out.reshape(ctx.shape), None, None, None, None, None
+
+
+def depth_smoothness_loss(depth, image=None, weight=None, order=1, normalize=True, edge_gamma=1.0):
+    """Edge-aware smoothness of the rendered depth: the disparity smoothness term of the self-supervised driving pipelines (Monodepth2's
+    get_smooth_loss, kornia's inverse_depth_smoothness_loss), defined on what the rasterizer renders under pipe.inv_depth.
+
+    depth: float32 [H, W] or [1, H, W], differentiable.  image: an optional float32 [C, H, W] guide (1 <= C <= 8; use the ground-truth
+    image), a constant.  weight: an optional supervision weight (see l1_ssim), a constant.  With Sw = sum w, m = sum w d / Sw and
+    s = 1 / (m + 1e-7) (s = 1 with normalize=False):
+        order 1, along x:  delta = d(x) - d(x+1),            v = w(x) w(x+1),         a = exp(-edge_gamma mean_c |I(x) - I(x+1)|)
+        order 2, along x:  delta = d(x-1) - 2 d(x) + d(x+1),  v = w(x-1) w(x) w(x+1),  a = exp(-edge_gamma mean_c (|I(x) - I(x-1)| + |I(x+1) - I(x)|) / 2)
+        loss = s (sum v a |delta| / sum v  [along x]  +  the same along y)
+    (a = 1 without an image).  Order 1 penalises every slanted surface; order 2 leaves planes -- whose inverse depth is affine in the pixel
+    coordinates: roads, walls -- unpenalised.  The differences are taken on the un-normalised depth and s multiplies the total: the loss of the
+    mean-normalised depth (it is homogeneous of degree 1), in one pass.  An axis without a term contributes 0, Sw = 0 gives 0 with a zero
+    gradient, both decided on the device.  One stencil pass and a one-block finish forward, one gather backward (include/adgs_loss.h)."""
+    who = "depth_smoothness_loss"
+    if not torch.is_tensor(depth):
+        raise TypeError("%s: depth must be a tensor, got %s" % (who, type(depth).__name__))
+    if depth.dim() not in (2, 3) or depth.numel() != depth.shape[-2] * depth.shape[-1]:
+        raise ValueError("%s: depth must be [H, W] or [1, H, W], got %s" % (who, tuple(depth.shape)))
+    if depth.dtype != torch.float32:
+        raise TypeError("%s: depth must be float32, got %s" % (who, depth.dtype))
+    H, W = depth.shape[-2:]
+    if order not in (1, 2):
+        raise ValueError("%s: order must be 1 or 2, got %r" % (who, order))
+    gamma = float(edge_gamma)
+    if not (0.0 <= gamma < float("inf")):
+        raise ValueError("%s: edge_gamma must be finite and >= 0, got %r" % (who, edge_gamma))
+    guide = None
+    if image is not None:
+        if not torch.is_tensor(image):
+            raise TypeError("%s: image must be a tensor, got %s" % (who, type(image).__name__))
+        if image.dim() != 3 or tuple(image.shape[1:]) != (H, W) or not 1 <= image.shape[0] <= 8:
+            raise ValueError("%s: image must be [C, H, W] = [1..8, %d, %d], got %s" % (who, H, W, tuple(image.shape)))
+        if image.dtype != torch.float32:
+            raise TypeError("%s: image must be float32, got %s" % (who, image.dtype))
+        if image.device != depth.device:
+            raise RuntimeError("%s: image is on %s, depth on %s" % (who, image.device, depth.device))
+        guide = image.detach().contiguous()
+    w = None if weight is None else _check_weight(weight, H, W, depth.device, who)
+    if not depth.is_cuda:
+        raise RuntimeError("%s: tensors must be on a HIP device; there is no CPU path" % who)
+    return _DepthSmooth.apply(depth, guide, w, int(order), int(bool(normalize)), gamma)
 
 
 # ---------------------------------------------------------------- neighbourhood regularisers (train.py:104-113)

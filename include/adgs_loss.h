@@ -123,6 +123,31 @@ int adgs_lidar_depth_loss_backward(int n, const float* depth, const float* lidar
 	const float* g_loss, float* dL_ddepth, void* stream);
 
 /*
+ * Edge-aware smoothness of the rendered depth (what the rasterizer renders under pipe.inv_depth: the disparity smoothness term of the
+ * self-supervised driving pipelines), first or second order.  depth: H*W floats, the differentiable input; guide: C*H*W floats (1 <= C <= 8)
+ * or NULL with C = 0, a constant; weight: H*W floats or NULL (= 1), a constant.  order is 1 or 2, gamma >= 0.
+ *   sum w = sum_p w_p,  m = sum_p w_p d_p / sum w,  s = 1 / (m + 1e-7) with normalize, else s = 1
+ *   order 1, x axis, for every (y, x) with x + 1 < W:   delta = d(y,x) - d(y,x+1),  v = w(y,x) w(y,x+1),
+ *       a = exp(-gamma (1/C) sum_c |I_c(y,x) - I_c(y,x+1)|)                                     (a = 1 without a guide)
+ *   order 2, x axis, for every x with 1 <= x <= W - 2:  delta = d(x-1) - 2 d(x) + d(x+1), formed in double from the float inputs,
+ *       v = w(x-1) w(x) w(x+1),  a = exp(-gamma (1/(2C)) sum_c (|I_c(x) - I_c(x-1)| + |I_c(x+1) - I_c(x)|))
+ *   S_x = sum v a |delta|,  V_x = sum v;  the y axis is the same along the columns;   L = s (S_x / V_x + S_y / V_y)
+ * An axis with V = 0 (too few pixels along it, or everything masked) contributes 0; sum w = 0 gives L = 0 and an all-zero gradient: both
+ * decided on the device.  The differences are taken on the UN-normalised depth and the scalar s multiplies the total (L is homogeneous of
+ * degree 1 in d, so this is the loss of the mean-normalised depth without a second pass -- and a plane keeps its exact zeros at order 2).
+ *   dL/dd_p = g s (G_p - [normalize] (w_p / sum w) L),   G_p = sum over the terms that contain p of coefficient sign(delta) v a / V
+ * (coefficient +-1 at order 1 and (1, -2, 1) at order 2; sign(0) = 0): the gradient through the mean needs no second reduction.
+ * work: ADGS_SMOOTH_WORK_DOUBLES device doubles: ADGS_LOSS_SLOTS x 8 slot rows (zero on entry and on return: the forward contains its finish
+ * kernel), then sum w d, sum w, S_x, V_x, S_y, V_y, s, L, which the backward reads -- keep the buffer until then.  loss: one device float;
+ * g_loss: a DEVICE scalar; every element of dL_ddepth is written.  H * W = 0 returns 0 and launches nothing.
+ */
+#define ADGS_SMOOTH_WORK_DOUBLES (256 * 8 + 8)
+int adgs_depth_smooth_forward(int H, int W, int C, const float* depth, const float* guide, const float* weight,
+	int order, int normalize, float gamma, double* work, float* loss, void* stream);
+int adgs_depth_smooth_backward(int H, int W, int C, const float* depth, const float* guide, const float* weight,
+	int order, int normalize, float gamma, const double* work, const float* g_loss, float* dL_ddepth, void* stream);
+
+/*
  * Neighbourhood regularisers of the training loop (train.py:104-113), over GaussianModel.obj_near_idx [G, K] (int64 rows of
  * the object range, scene/gaussian_model.py:825-833):
  *   reg_loss       = mean(sum(var(xyz_deform_param[obj_near_idx], dim=1), dim=-1))   x = xyz_deform_param [N,3,C]: D = 3 C, inner = C
