@@ -144,6 +144,12 @@ SIGNATURES = {
     "adgs_cc_work_doubles": (ctypes.c_size_t, []),
     "adgs_cc_fit": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_cc_apply": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p]),
+    # include/adgs_normals.h
+    "adgs_gaussian_normals_forward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "adgs_gaussian_normals_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "adgs_normal_consistency_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p, c_p]),
+    "adgs_normal_consistency_backward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_depth_to_normal": (c_i, [c_i, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

@@ -137,12 +137,20 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
     pipe.filter_3d (extension, read with getattr, default off): the 3D smoothing filter of Mip-Splatting -- the rasterizer receives
     adgs.filter3d.apply(scales, opacity, pc.filter_3D) instead of the deformation pass's scales and opacity (pc.compute_3d_filter(cameras)
     first, and again after every densification).  The result's 'opacity' / 'scales' entries stay the unfiltered ones, which is what
-    densification and pruning read.  A model on the raw-scene path materialises its scene rows for such a frame."""
+    densification and pruning read.  A model on the raw-scene path materialises its scene rows for such a frame.
+    pipe.render_normals (extension, read with getattr, default off): the result also carries 'img_normal' [3,H,W], the blend of the
+    Gaussians' camera-space normals (adgs.normals.gaussian_normals: the shortest axis of each Gaussian, facing the camera) -- three more
+    semantic channels behind the object mask, for adgs.normals.normal_consistency_loss; 'img_semantic' stays what it is without the flag.
+    Not together with pipe.absgrad while gradients are enabled.  A model on the raw-scene path materialises its scene rows for such a frame."""
     n_pts = pc.get_pts_num if hasattr(pc, "get_pts_num") else pc.get_xyz.shape[0]
     device = (pc._scene_xyz if hasattr(pc, "_scene_xyz") else pc.get_xyz).device
     # the densification statistics read the gradient of the screen-space means from this tensor (.grad[:, :2])
     means2D = screenspace_points(n_pts, device)
     means2D_abs = screenspace_points(n_pts, device) if (bool(getattr(pipe, "absgrad", False)) and torch.is_grad_enabled()) else None
+    render_normals = bool(getattr(pipe, "render_normals", False))
+    if render_normals and means2D_abs is not None:
+        raise RuntimeError("pipe.render_normals cannot be combined with pipe.absgrad while gradients are enabled: the rasterizer's backward cannot form "
+                           "the absolute gradient sums together with gradients of more than one semantic channel")
 
     rasterizer = GaussianRasterizer(raster_settings=_camera_settings(viewpoint_camera, pc, pipe, scaling_modifier, device))
     filter_3d = None
@@ -151,13 +159,19 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
         if filter_3d is None or filter_3d.shape[0] != n_pts:
             raise RuntimeError("pipe.filter_3d is on but the model has %s: call compute_3d_filter(cameras) before rendering and after every densification" % (
                 "no 3D filter" if filter_3d is None else "a 3D filter of %d rows for %d Gaussians" % (filter_3d.shape[0], n_pts)))
-    pkg, flow_points = _deformed_state(pc, viewpoint_camera.time, flow_pkg, full_rows=override_color is not None or filter_3d is not None)
+    pkg, flow_points = _deformed_state(pc, viewpoint_camera.time, flow_pkg, full_rows=override_color is not None or filter_3d is not None or render_normals)
     raster_pkg = pkg
     if filter_3d is not None:
         from adgs import filter3d as _filter3d
         raster_pkg = dict(pkg)
         raster_pkg["scales"], raster_pkg["opacity"] = _filter3d.apply(pkg["scales"] if "scales" in pkg else pc.get_scaling, pkg["opacity"], filter_3d)
     semantic = (pc.obj_mask_float if hasattr(pc, "obj_mask_float") else pc.get_obj_mask.float()[..., None]) if render_objmask else None
+    if render_normals:
+        # mask (when asked) and normal in one [N, 1 + 3] tensor, no cat.  The unfiltered scales: the 3D filter adds the same variance to
+        # every axis, the shortest stays the shortest
+        from adgs import normals as _normals
+        semantic = _normals.gaussian_normals(pkg["scales"] if "scales" in pkg else pc.get_scaling, pkg["rotation"], pkg["xyz"],
+                                             rasterizer.raster_settings.viewmatrix, mask=semantic)
     # the environment-map background first: on the raw-SH path the blend epilogue composites it (`render = C + T * background`,
     # gaussian_renderer/__init__.py:93-94) and the blend backward returns dL/dbackground = T * dL/drender -- no element-wise pass
     background = env_map.get_image_background(viewpoint_camera) if env_map is not None else None
@@ -170,6 +184,10 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
         if background is None:
             background = torch.zeros_like(foreground)
         rendered = foreground + (1.0 - img_opacity) * background
+    img_normal = None
+    if render_normals:
+        c0 = semantic.shape[1] - 3
+        img_normal, img_semantic = img_semantic[c0:], (img_semantic[:1] if c0 else None)
     shs = pkg.get("shs")
     if shs is not None and not torch.is_tensor(shs) and getattr(shs, "scene_xyz", None) is not None:
         # raw-scene path: rows [0, Ns) of the deformed tensors were never written; hand them out lazily (a full deformation pass)
@@ -189,6 +207,8 @@ def render(viewpoint_camera, pc, env_map, pipe, scaling_modifier=1.0, override_c
                depth=depth.squeeze(0), img_opacity=img_opacity.squeeze(0),
                background=background, img_flow=img_flow if flow_points is not None else None,
                img_semantic=img_semantic if semantic is not None else None)
+    if render_normals:
+        out["img_normal"] = img_normal
     if means2D_abs is not None:
         out["viewspace_points_abs"] = means2D_abs
     if foreground is not None:
