@@ -9,6 +9,7 @@
 // does not fit the LDS budget (a small image under a large grid) runs the same kernels without LDS -- gathers from / atomics into
 // global memory.  adgs_test_bilagrid_path (include/adgs_testing.h) reports that choice.
 #include "common.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_bilagrid.h"
 #include "../../include/adgs_testing.h"
 #include <algorithm>
@@ -214,11 +215,11 @@ __global__ void __launch_bounds__(256) bg_slice_bwd_kernel(BgShape s, const floa
 
 // ---------------------------------------------------------------- total variation
 struct TvShape { int L, Hg, Wg; long long total; float wz, wy, wx; };      // w_axis = 1 / (N 12 pairs along the axis per channel)
-constexpr int TV_SLOTS = ADGS_BILAGRID_TV_WORK_DOUBLES;
+constexpr int TV_SLOTS = ADGS_BILAGRID_TV_WORK_DOUBLES;      // slot rows of one double (slot_reduce.h), nothing behind them
 
-__global__ void __launch_bounds__(256) bg_tv_sum_kernel(TvShape s, const float* __restrict__ g, double* __restrict__ work) {
+__global__ void __launch_bounds__(SLOT_THREADS) bg_tv_sum_kernel(TvShape s, const float* __restrict__ g, double* __restrict__ work) {
 	const int plane = s.Hg * s.Wg;
-	double sum = 0;
+	double sum[1] = { 0 };
 	for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < s.total; e += (long long)gridDim.x * blockDim.x) {
 		const long long row = e / s.Wg, lev = row / s.Hg;
 		const int x = (int)(e - row * s.Wg), y = (int)(row - lev * s.Hg), z = (int)(lev % s.L);
@@ -227,21 +228,14 @@ __global__ void __launch_bounds__(256) bg_tv_sum_kernel(TvShape s, const float* 
 		if (x + 1 < s.Wg) { const float q = g[e + 1] - v; acc += s.wx * q * q; }
 		if (y + 1 < s.Hg) { const float q = g[e + s.Wg] - v; acc += s.wy * q * q; }
 		if (z + 1 < s.L) { const float q = g[e + plane] - v; acc += s.wz * q * q; }
-		sum += (double)acc;
+		sum[0] += (double)acc;
 	}
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (blockIdx.x * 4 + threadIdx.x / WAVE) % TV_SLOTS, sum);
+	slot_add_wave<TV_SLOTS, 1>(work, sum);
 }
-__global__ void __launch_bounds__(256) bg_tv_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
-	__shared__ double s[256 / WAVE];
-	double a = work[threadIdx.x];
-	work[threadIdx.x] = 0.0;                             // consumed: zero again for the next call on this buffer
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) a += __shfl_xor(a, off, WAVE);
-	if ((threadIdx.x & (WAVE - 1)) == 0) s[threadIdx.x / WAVE] = a;
-	__syncthreads();
-	if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[w]; loss[0] = (float)t; }
+__global__ void __launch_bounds__(SLOT_THREADS) bg_tv_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
+	double t[1];
+	slot_finish<TV_SLOTS, 1>(work, t);
+	if (threadIdx.x == 0) loss[0] = (float)t[0];
 }
 __global__ void __launch_bounds__(256) bg_tv_bwd_kernel(TvShape s, const float* __restrict__ g, const float* __restrict__ g_loss, float* __restrict__ dg) {
 	const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -327,8 +321,8 @@ extern "C" int adgs_bilagrid_tv_forward(int N, int L, int Hg, int Wg, const floa
 	if (bg_check_tv(s, N, L, Hg, Wg, "adgs_bilagrid_tv_forward") != 0) return -1;
 	if (!grids || !work || !loss) { set_error("adgs_bilagrid_tv_forward: NULL grids / work / loss"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	hipLaunchKernelGGL(bg_tv_sum_kernel, dim3((unsigned)std::min<long long>((s.total + 255) / 256, 2048)), dim3(256), 0, stream, s, grids, work);
-	hipLaunchKernelGGL(bg_tv_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(bg_tv_sum_kernel, dim3(reduce_blocks(s.total)), dim3(SLOT_THREADS), 0, stream, s, grids, work);
+	hipLaunchKernelGGL(bg_tv_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

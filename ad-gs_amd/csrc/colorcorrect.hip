@@ -7,6 +7,7 @@
 // accumulators (130 VGPRs) live at a time, and their cross-lane reduction is paid once per workgroup and channel, not per tile.  The
 // image is read once per channel; at the evaluation resolution it stays in the Infinity Cache between the three sweeps.
 #include "common.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_colorcorrect.h"
 #include <cmath>
 
@@ -121,8 +122,7 @@ template <int MODEL> __global__ void __launch_bounds__(CT) cc_accumulate_kernel(
 #pragma unroll
 				for (int j = i; j <= N; j++, a++) {      // j == N: h_i
 					double v = j < N ? acc[a - i] : acc[N * (N + 1) / 2 + i];
-#pragma unroll
-					for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+					wave_sum(v);
 					if ((tid & (WAVE - 1)) == 0) red[j < N ? tri(M::feat(i), M::feat(j)) : NG + M::feat(i)][tid / WAVE] = v;
 				}
 			}

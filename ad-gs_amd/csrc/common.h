@@ -55,6 +55,10 @@ void set_error(const std::string& msg);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// sign(d) as a float, 0 at 0 and at NaN (torch.abs backward); the comparison is made in the argument's type
+__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+__device__ __forceinline__ float sgn(double d) { return d > 0.0 ? 1.f : (d < 0.0 ? -1.f : 0.f); }
+
 // Sub-allocator over a caller-provided chunk (the role of `obtain` in
 // RAST/cuda_rasterizer/rasterizer_impl.h:22-28); 256-byte alignment.
 struct Carver {

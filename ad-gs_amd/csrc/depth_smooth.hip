@@ -13,8 +13,8 @@
 //
 // Ownership.  A pair belongs to its first pixel, a triple to its centre: a term that straddles a tile border is summed by exactly one workgroup.
 // delta is formed in double from the float inputs (its sign is then the float64 reference's), the products v a |delta| in float, the six sums
-// (sum w d, sum w, S_x, V_x, S_y, V_y) in double per thread, then per wave (__shfl_xor), then into slot row (block * 4 + wave) % ADGS_LOSS_SLOTS.
-// The one-block finish kernel adds the rows up, leaves them zero and stores the totals, s and L behind them.
+// (sum w d, sum w, S_x, V_x, S_y, V_y) in double per thread, then through the slot rows (slot_reduce.h); the finish kernel stores the totals,
+// s and L behind the rows.
 //
 // Backward: a gather.  Every staged pixel that owns a term stores sign(delta) v a once (cx, cy in LDS); a pixel then collects the <= 4 (order 1)
 // or <= 6 (order 2) coefficients of the terms it takes part in -- halo 1 or 2 -- and writes its element of dL_ddepth once: no atomics, no zero fill.
@@ -22,6 +22,7 @@
 // Byte model (HBM): forward reads (1 + C + [weight]) * 4 * H * W bytes and writes nothing but the slot rows; backward reads the same and
 // writes 4 * H * W.  No intermediate image goes to global memory.
 #include "common.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_loss.h"
 #include <climits>
 #include <cmath>
@@ -33,7 +34,7 @@ constexpr int DS_TX = 32, DS_TY = 16, DS_LT = 256;
 constexpr int DS_CH = 4;                                        // guide channels in flight per thread
 constexpr int DS_ROW = 8;                                       // doubles per slot row (six used)
 constexpr int DS_MAX_TILES = (1 << 24) - 1;                     // tiles * 256 threads must stay below 2^32
-static_assert(ADGS_LOSS_SLOTS == 256 && ADGS_SMOOTH_WORK_DOUBLES >= ADGS_LOSS_SLOTS * DS_ROW + 8, "one finish thread per slot row; eight scalars behind the rows");
+static_assert(DS_LT == SLOT_THREADS && ADGS_SMOOTH_WORK_DOUBLES >= ADGS_LOSS_SLOTS * DS_ROW + 8, "slot_add_wave's workgroup; eight scalars behind the rows");
 // scalars behind the rows: sum w d, sum w, S_x, V_x, S_y, V_y, s, L
 enum { DS_SWD = 0, DS_SW, DS_SX, DS_VX, DS_SY, DS_VY, DS_S, DS_L };
 
@@ -152,34 +153,16 @@ __global__ void __launch_bounds__(DS_LT) depth_smooth_sum_kernel(int H, int W, i
 		smooth_term<ORDER>(sd, sw, ey, i, R::RX, kx, delta, v, a);
 		acc[DS_SY] += (double)(v * a * (float)fabs(delta)); acc[DS_VY] += (double)v;
 	}
-#pragma unroll
-	for (int q = 0; q < 6; q++) {
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off, WAVE);
-	}
-	if ((tid & (WAVE - 1)) == 0) {
-		double* row = work + (size_t)((blockIdx.x * 4u + (unsigned)(tid / WAVE)) % ADGS_LOSS_SLOTS) * DS_ROW;
-#pragma unroll
-		for (int q = 0; q < 6; q++) atomicAdd(row + q, acc[q]);
-	}
+	slot_add_wave<ADGS_LOSS_SLOTS, DS_ROW>(work, acc);
 }
 
 // one block: totals of the slot rows (left zero) -> the eight scalars behind them and the loss
-__global__ void __launch_bounds__(256) depth_smooth_finish_kernel(double* __restrict__ work, int normalize, float* __restrict__ loss) {
-	__shared__ double s[6][256 / WAVE];
-	double v[6];
-#pragma unroll
-	for (int q = 0; q < 6; q++) {
-		v[q] = work[(size_t)threadIdx.x * DS_ROW + q];
-		work[(size_t)threadIdx.x * DS_ROW + q] = 0.0;              // consumed
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
-	}
-	__syncthreads();
+__global__ void __launch_bounds__(SLOT_THREADS) depth_smooth_finish_kernel(double* __restrict__ work, int normalize, float* __restrict__ loss) {
+	double t[6];
+	slot_finish<ADGS_LOSS_SLOTS, DS_ROW>(work, t);
 	if (threadIdx.x == 0) {
 		double* tot = work + (size_t)ADGS_LOSS_SLOTS * DS_ROW;
-		for (int q = 0; q < 6; q++) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[q][w]; tot[q] = t; }
+		for (int q = 0; q < 6; q++) tot[q] = t[q];
 		double sc = 0.0, L = 0.0;
 		if (tot[DS_SW] > 0.0) {
 			sc = normalize ? 1.0 / (tot[DS_SWD] / tot[DS_SW] + 1e-7) : 1.0;
@@ -208,11 +191,11 @@ __global__ void __launch_bounds__(DS_LT) depth_smooth_bwd_kernel(int H, int W, i
 		double delta; float v, a, tx = 0.f, ty = 0.f;
 		if (rx >= ORDER - 1 && rx + 1 < R::RX) {
 			smooth_term<ORDER>(sd, sw, ex, i, 1, kx, delta, v, a);
-			tx = (delta > 0.0 ? 1.f : (delta < 0.0 ? -1.f : 0.f)) * (v * a);
+			tx = sgn(delta) * (v * a);
 		}
 		if (ry >= ORDER - 1 && ry + 1 < R::RY) {
 			smooth_term<ORDER>(sd, sw, ey, i, R::RX, kx, delta, v, a);
-			ty = (delta > 0.0 ? 1.f : (delta < 0.0 ? -1.f : 0.f)) * (v * a);
+			ty = sgn(delta) * (v * a);
 		}
 		cx[i] = tx; cy[i] = ty;
 	}
@@ -267,7 +250,7 @@ extern "C" int adgs_depth_smooth_forward(int H, int W, int C, const float* depth
 	const float k = smooth_k(C, order, gamma);
 	if (order == 1) hipLaunchKernelGGL(depth_smooth_sum_kernel<1>, dim3((unsigned)tiles), dim3(DS_LT), 0, stream, H, W, C, tiles_x, depth, guide, weight, k, work);
 	else hipLaunchKernelGGL(depth_smooth_sum_kernel<2>, dim3((unsigned)tiles), dim3(DS_LT), 0, stream, H, W, C, tiles_x, depth, guide, weight, k, work);
-	hipLaunchKernelGGL(depth_smooth_finish_kernel, dim3(1), dim3(256), 0, stream, work, normalize ? 1 : 0, loss);
+	hipLaunchKernelGGL(depth_smooth_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, normalize ? 1 : 0, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

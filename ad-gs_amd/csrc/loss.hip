@@ -8,8 +8,8 @@
 // now 99 + 75.  The arithmetic per output (tap order, fused multiply-adds) is unchanged.
 #include "common.h"
 #include "ssim_window.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_loss.h"
-#include <algorithm>
 
 namespace adgs {
 namespace {
@@ -27,7 +27,6 @@ __global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const flo
 	constexpr int NS = WEIGHTED ? 3 : 2;
 	__shared__ __attribute__((aligned(16))) float s1[HSY][SSTR], s2[HSY][SSTR];
 	__shared__ __attribute__((aligned(16))) float h[5][HSY][HSTR];      // horizontally filtered x1, x2, x1^2, x2^2, x1 x2
-	__shared__ double red[NS][LT / WAVE];
 	const int tid = threadIdx.x;
 	const int x0 = blockIdx.x * TSX, y0 = blockIdx.y * TSY;
 	const size_t plane = (size_t)blockIdx.z * H * W;
@@ -119,22 +118,9 @@ __global__ void __launch_bounds__(LT) l1_ssim_fwd_kernel(int H, int W, const flo
 			d_mu1[oo] = p_mu1; d_e11[oo] = p_e11; d_e12[oo] = p_e12;
 		}
 	}
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) {
-		l1 += __shfl_xor(l1, off, WAVE); sm += __shfl_xor(sm, off, WAVE);
-		if constexpr (WEIGHTED) sw += __shfl_xor(sw, off, WAVE);
-	}
-	if ((tid & (WAVE - 1)) == 0) {
-		red[0][tid / WAVE] = l1; red[1][tid / WAVE] = sm;
-		if constexpr (WEIGHTED) red[2][tid / WAVE] = sw;
-	}
-	__syncthreads();
-	if (tid < NS) {
-		double t = 0.0;
-		for (int w = 0; w < LT / WAVE; w++) t += red[tid][w];
-		const unsigned b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-		atomicAdd(sums + NS * (b % ADGS_LOSS_SLOTS) + tid, t);
-	}
+	double v[NS] = { l1, sm };
+	if constexpr (WEIGHTED) v[2] = sw;
+	slot_add_block<ADGS_LOSS_SLOTS, NS, LT>(sums, v);
 }
 
 // WEIGHTED: the maps arrive times w (see the forward), the L1 term takes w at the pixel, and 1 / (planes sum w) replaces inv_n: sum w is
@@ -194,49 +180,34 @@ __global__ void __launch_bounds__(LT) l1_ssim_bwd_kernel(int H, int W, const flo
 		const size_t oo = plane + (size_t)gy * W + gx;
 		const float x1 = img[oo], x2 = gt[oo];
 		const float dx = x1 - x2;
-		float sgn = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f);                   // torch.abs backward: sign(), 0 at 0
-		if constexpr (WEIGHTED) sgn *= weight[(size_t)gy * W + gx];
-		out[oo] = gl * sgn * inv_n + gs * inv_n * (acc[0][o] + 2.f * x1 * acc[1][o] + x2 * acc[2][o]);
+		float sg = sgn(dx);
+		if constexpr (WEIGHTED) sg *= weight[(size_t)gy * W + gx];
+		out[oo] = gl * sg * inv_n + gs * inv_n * (acc[0][o] + 2.f * x1 * acc[1][o] + x2 * acc[2][o]);
 	}
 }
 
 // ---------------------------------------------------------------- scale/shift-invariant depth loss
-// work layout (doubles): [slot][8] partial sums (a00, a01, a11, b0, b1 of pass 1; L1, A = sum m sgn p, B = sum m sgn of pass 2),
+// work layout (doubles): [slot][DEPTH_ROW] partial sums (a00, a01, a11, b0, b1 of pass 1; L1, A = sum m sgn p, B = sum m sgn of pass 2),
 // then 16 scalars: [0..4] the five totals, [5] s, [6] t, [7] det, [8] L1 total, [9] A, [10] B.
-constexpr int DSLOTS = 256;
+constexpr int DEPTH_ROW = 8, DEPTH_TOTALS = ADGS_LOSS_SLOTS * DEPTH_ROW;
 struct DepthScalars { double a00, a01, a11, b0, b1, s, t, det; };
 
-__global__ void __launch_bounds__(256) depth_sums_kernel(int n, const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m, double* __restrict__ work) {
+__global__ void __launch_bounds__(SLOT_THREADS) depth_sums_kernel(int n, const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m, double* __restrict__ work) {
 	double a00 = 0, a01 = 0, a11 = 0, b0 = 0, b1 = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
 		const double w = m ? (double)m[i] : 1.0, x = p[i], y = g[i];
 		a00 += w * x * x; a01 += w * x; a11 += w; b0 += w * x * y; b1 += w * y;
 	}
 	double v[5] = { a00, a01, a11, b0, b1 };
-#pragma unroll
-	for (int q = 0; q < 5; q++) {
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % DSLOTS) * 8 + q, v[q]);
-	}
+	slot_add_wave<ADGS_LOSS_SLOTS, DEPTH_ROW>(work, v);
 }
 // one block: totals of the slots -> scale, shift (depth_utils.py:30-45)
-__global__ void __launch_bounds__(256) depth_solve_kernel(double* __restrict__ work) {
-	__shared__ double s[5][256 / WAVE];
-	double* out = work + (size_t)DSLOTS * 8;
-	double v[5];
-#pragma unroll
-	for (int q = 0; q < 5; q++) {
-		v[q] = work[(size_t)threadIdx.x * 8 + q];
-		work[(size_t)threadIdx.x * 8 + q] = 0.0;      // consumed (see aux_finish_kernel)
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
-	}
-	__syncthreads();
+__global__ void __launch_bounds__(SLOT_THREADS) depth_solve_kernel(double* __restrict__ work) {
+	double* out = work + DEPTH_TOTALS;
+	double t[5];
+	slot_finish<ADGS_LOSS_SLOTS, DEPTH_ROW>(work, t);
 	if (threadIdx.x == 0) {
-		double t[5];
-		for (int q = 0; q < 5; q++) { t[q] = 0; for (int w = 0; w < 256 / WAVE; w++) t[q] += s[q][w]; out[q] = t[q]; }
+		for (int q = 0; q < 5; q++) out[q] = t[q];
 		// the reference forms the sums and the determinant in fp32 (torch.sum of fp32 tensors): round the totals first
 		const float a00 = (float)t[0], a01 = (float)t[1], a11 = (float)t[2], b0 = (float)t[3], b1 = (float)t[4];
 		const float det = a00 * a11 - a01 * a01;
@@ -245,39 +216,25 @@ __global__ void __launch_bounds__(256) depth_solve_kernel(double* __restrict__ w
 		out[5] = sc; out[6] = sh; out[7] = det;
 	}
 }
-__global__ void __launch_bounds__(256) depth_l1_kernel(int n, const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m, double* __restrict__ work) {
-	const double* sc = work + (size_t)DSLOTS * 8;
+__global__ void __launch_bounds__(SLOT_THREADS) depth_l1_kernel(int n, const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m, double* __restrict__ work) {
+	const double* sc = work + DEPTH_TOTALS;
 	const float s = (float)sc[5], t = (float)sc[6];
 	double L = 0, A = 0, B = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
 		const float w = m ? m[i] : 1.f, x = p[i];
 		const float d = (s * x + t) - g[i];
-		const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+		const float sg = sgn(d);
 		L += (double)(fabsf(d) * w); A += (double)(w * sg * x); B += (double)(w * sg);
 	}
 	double v[3] = { L, A, B };
-#pragma unroll
-	for (int q = 0; q < 3; q++) {
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % DSLOTS) * 8 + 5 + q, v[q]);
-	}
+	slot_add_wave<ADGS_LOSS_SLOTS, DEPTH_ROW>(work, v, 5);      // columns 5 .. 7 of the rows
 }
-__global__ void __launch_bounds__(256) depth_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
-	__shared__ double s[3][256 / WAVE];
-	double* out = work + (size_t)DSLOTS * 8;
-	double v[3];
-#pragma unroll
-	for (int q = 0; q < 3; q++) {
-		v[q] = work[(size_t)threadIdx.x * 8 + 5 + q];
-		work[(size_t)threadIdx.x * 8 + 5 + q] = 0.0;
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
-	}
-	__syncthreads();
+__global__ void __launch_bounds__(SLOT_THREADS) depth_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
+	double* out = work + DEPTH_TOTALS;
+	double t[3];
+	slot_finish<ADGS_LOSS_SLOTS, DEPTH_ROW>(work, t, 5);
 	if (threadIdx.x == 0) {
-		for (int q = 0; q < 3; q++) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[q][w]; out[8 + q] = t; }
+		for (int q = 0; q < 3; q++) out[8 + q] = t[q];
 		loss[0] = (float)(out[8] / out[2]);                       // sum(|.| m) / sum(m)
 	}
 }
@@ -285,11 +242,11 @@ __global__ void __launch_bounds__(256) depth_bwd_kernel(int n, const float* __re
 	const double* __restrict__ work, const float* __restrict__ g_loss, float* __restrict__ out) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const double* sc = work + (size_t)DSLOTS * 8;
+	const double* sc = work + DEPTH_TOTALS;
 	const double a00 = sc[0], a01 = sc[1], a11 = sc[2], b0 = sc[3], b1 = sc[4], s = sc[5], t = sc[6], det = sc[7], A = sc[9], B = sc[10];
 	const float w = m ? m[i] : 1.f, x = p[i], y = g[i];
 	const float d = ((float)s * x + (float)t) - y;
-	const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+	const float sg = sgn(d);
 	double grad = (double)sg * s;
 	if (det != 0.0) {
 		// through the least-squares solution: s, t depend on a00 = sum m p^2, a01 = sum m p, b0 = sum m p g
@@ -303,9 +260,9 @@ __global__ void __launch_bounds__(256) depth_bwd_kernel(int n, const float* __re
 
 // ---------------------------------------------------------------- flow re-projection loss and clipped BCE
 // Pixel-wise losses of train.py:88-103 that the reference builds from nonzero() (a host synchronisation), gathers and half a
-// dozen elementwise kernels each.  Here: one reduction pass (double partial sums in AUX_SLOTS slots) + a one-thread finish,
-// and one elementwise backward.  aux work layout (doubles): [slot][2] = (sum, count), then [2*AUX_SLOTS] = sum, [+1] = count.
-constexpr int AUX_SLOTS = 256;
+// dozen elementwise kernels each.  Here: one reduction pass (slot_reduce.h) + a one-block finish, and one elementwise backward.
+// aux work layout (doubles): [slot][AUX_ROW] = (sum, count), then [AUX_TOTALS] = sum, [+1] = count.
+constexpr int AUX_ROW = 2, AUX_TOTALS = ADGS_LOSS_SLOTS * AUX_ROW;
 struct FlowCam { float M[9]; float KT[3]; float dist; };          // M = K R, KT = K T (3x3 row-major products formed on the host in fp32)
 // The camera of the flow target as DEVICE pointers (the reference keeps K / R / T on the GPU, train.py:68-71): nothing is read back
 // and nothing is cached on the host.  K == nullptr: the by-value FlowCam is used.
@@ -343,7 +300,7 @@ __device__ __forceinline__ FlowPix flow_pixel(int i, int HW, int W, int H, const
 	r.w = (op ? op[i] : 1.f) * (r.front ? 1.f : 0.f);
 	return r;
 }
-__global__ void __launch_bounds__(256) flow_loss_sum_kernel(int H, int W, const float* __restrict__ f, const float* __restrict__ fl,
+__global__ void __launch_bounds__(SLOT_THREADS) flow_loss_sum_kernel(int H, int W, const float* __restrict__ f, const float* __restrict__ fl,
 	const float* __restrict__ vis, const float* __restrict__ op, FlowCam c0, FlowCamDev cd, double* __restrict__ work) {
 	const int HW = H * W;
 	const FlowCam c = flow_cam_load(c0, cd);
@@ -355,26 +312,16 @@ __global__ void __launch_bounds__(256) flow_loss_sum_kernel(int H, int W, const 
 			sum += (double)((fabsf(p.u - fl[i]) / (float)W + fabsf(p.v - fl[HW + i]) / (float)H) * p.w);      // :103-105
 		}
 	}
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, WAVE); cnt += __shfl_xor(cnt, off, WAVE); }
-	if ((threadIdx.x & (WAVE - 1)) == 0) {
-		const size_t slot = (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2;
-		atomicAdd(work + slot, sum); atomicAdd(work + slot + 1, cnt);
-	}
+	double v[2] = { sum, cnt };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 }
-__global__ void __launch_bounds__(256) aux_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
-	__shared__ double s[2][256 / WAVE];
-	double a = work[(size_t)threadIdx.x * 2], b = work[(size_t)threadIdx.x * 2 + 1];
-	work[(size_t)threadIdx.x * 2] = 0.0; work[(size_t)threadIdx.x * 2 + 1] = 0.0;      // consumed: the slot region is zero again for the next call on this buffer (include/adgs_loss.h)
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) { a += __shfl_xor(a, off, WAVE); b += __shfl_xor(b, off, WAVE); }
-	if ((threadIdx.x & (WAVE - 1)) == 0) { s[0][threadIdx.x / WAVE] = a; s[1][threadIdx.x / WAVE] = b; }
-	__syncthreads();
+// the finish kernel every (sum, count) term shares: the two totals behind the rows, loss = sum / count
+__global__ void __launch_bounds__(SLOT_THREADS) aux_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
+	double t[2];
+	slot_finish<ADGS_LOSS_SLOTS, AUX_ROW>(work, t);
 	if (threadIdx.x == 0) {
-		double ta = 0, tb = 0;
-		for (int w = 0; w < 256 / WAVE; w++) { ta += s[0][w]; tb += s[1][w]; }
-		work[2 * AUX_SLOTS] = ta; work[2 * AUX_SLOTS + 1] = tb;
-		loss[0] = tb > 0 ? (float)(ta / tb) : 0.f;                   // mean over the selected pixels; 0.0 when none (:92-93)
+		work[AUX_TOTALS] = t[0]; work[AUX_TOTALS + 1] = t[1];
+		loss[0] = t[1] > 0 ? (float)(t[0] / t[1]) : 0.f;             // mean over the selected pixels; 0.0 when none (:92-93)
 	}
 }
 __global__ void __launch_bounds__(256) flow_loss_bwd_kernel(int H, int W, const float* __restrict__ f, const float* __restrict__ fl,
@@ -384,15 +331,14 @@ __global__ void __launch_bounds__(256) flow_loss_bwd_kernel(int H, int W, const 
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= HW) return;
 	const FlowCam c = flow_cam_load(c0, cd);
-	const double n = work[2 * AUX_SLOTS + 1];
+	const double n = work[AUX_TOTALS + 1];
 	const FlowPix p = flow_pixel(i, HW, W, H, f, fl, vis, op, c);
 	float gx = 0.f, gy = 0.f, gz = 0.f, go = 0.f;
 	if (p.sel && n > 0) {
 		const float gl = (float)((double)g_loss[0] / n);
 		const float du = p.u - fl[i], dv = p.v - fl[HW + i];
 		go = gl * (fabsf(du) / (float)W + fabsf(dv) / (float)H) * (p.front ? 1.f : 0.f);
-		const float su = du > 0.f ? 1.f : (du < 0.f ? -1.f : 0.f), sv = dv > 0.f ? 1.f : (dv < 0.f ? -1.f : 0.f);
-		const float gu = gl * su * p.w / (float)W, gv = gl * sv * p.w / (float)H;
+		const float gu = gl * sgn(du) * p.w / (float)W, gv = gl * sgn(dv) * p.w / (float)H;
 		// u = px / z, v = py / z; z = max(pz, dist) passes the gradient where pz > dist (the weight is 0 elsewhere)
 		const float gpx = gu / p.z, gpy = gv / p.z, gpz = -(gu * p.px + gv * p.py) / (p.z * p.z);
 		gx = c.M[0] * gpx + c.M[3] * gpy + c.M[6] * gpz;
@@ -420,14 +366,13 @@ __device__ __forceinline__ float bce_dpred(float x, float target, float lo, floa
 	inside = x >= lo && x <= hi;
 	return invert ? -dq : dq;
 }
-__global__ void __launch_bounds__(256) bce_clip_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target, float lo, float hi,
+__global__ void __launch_bounds__(SLOT_THREADS) bce_clip_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target, float lo, float hi,
 	int invert, int positive, double* __restrict__ work) {
 	double sum = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 		sum += (double)bce_value(pred[i], target[i], lo, hi, invert, positive);
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2, sum);
+	double v[1] = { sum };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 	if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(work + 1, (double)n);      // the "count" of the shared finish kernel
 }
 __global__ void __launch_bounds__(256) bce_clip_bwd_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target, float lo, float hi,
@@ -439,15 +384,7 @@ __global__ void __launch_bounds__(256) bce_clip_bwd_kernel(int n, const float* _
 	out[i] = inside ? g_loss[0] * d / (float)n : 0.f;
 }
 // the same with a per-element weight: sum w bce / sum w; the finish kernel's "count" is sum w, which the backward reads from the work buffer
-__device__ __forceinline__ void aux_add2(double sum, double cnt, double* __restrict__ work) {
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, WAVE); cnt += __shfl_xor(cnt, off, WAVE); }
-	if ((threadIdx.x & (WAVE - 1)) == 0) {
-		const size_t slot = (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2;
-		atomicAdd(work + slot, sum); atomicAdd(work + slot + 1, cnt);
-	}
-}
-__global__ void __launch_bounds__(256) bce_clip_weighted_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target,
+__global__ void __launch_bounds__(SLOT_THREADS) bce_clip_weighted_sum_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target,
 	const float* __restrict__ weight, float lo, float hi, int invert, int positive, double* __restrict__ work) {
 	double sum = 0, cnt = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -455,14 +392,15 @@ __global__ void __launch_bounds__(256) bce_clip_weighted_sum_kernel(int n, const
 		sum += (double)w * (double)bce_value(pred[i], target[i], lo, hi, invert, positive);
 		cnt += (double)w;
 	}
-	aux_add2(sum, cnt, work);
+	double v[2] = { sum, cnt };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 }
 __global__ void __launch_bounds__(256) bce_clip_weighted_bwd_kernel(int n, const float* __restrict__ pred, const float* __restrict__ target,
 	const float* __restrict__ weight, float lo, float hi, int invert, int positive, const double* __restrict__ work, const float* __restrict__ g_loss,
 	float* __restrict__ out) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const double sw = work[2 * AUX_SLOTS + 1];
+	const double sw = work[AUX_TOTALS + 1];
 	bool inside;
 	const float d = bce_dpred(pred[i], target[i], lo, hi, invert, positive, inside);
 	out[i] = inside && sw > 0.0 ? g_loss[0] * weight[i] * d * (float)(1.0 / sw) : 0.f;
@@ -477,7 +415,7 @@ __device__ __forceinline__ bool lidar_residual(float depth, float lidar, float m
 	r = (double)depth - (inv_depth ? 1.0 / (double)lidar : (double)lidar);
 	return true;
 }
-__global__ void __launch_bounds__(256) lidar_depth_sum_kernel(int n, const float* __restrict__ depth, const float* __restrict__ lidar, const float* __restrict__ mask,
+__global__ void __launch_bounds__(SLOT_THREADS) lidar_depth_sum_kernel(int n, const float* __restrict__ depth, const float* __restrict__ lidar, const float* __restrict__ mask,
 	int inv_depth, double* __restrict__ work) {
 	double sum = 0, cnt = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -485,18 +423,19 @@ __global__ void __launch_bounds__(256) lidar_depth_sum_kernel(int n, const float
 		double r;
 		if (lidar_residual(depth[i], lidar[i], m, inv_depth, r)) { sum += (double)m * fabs(r); cnt += (double)m; }
 	}
-	aux_add2(sum, cnt, work);
+	double v[2] = { sum, cnt };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 }
 __global__ void __launch_bounds__(256) lidar_depth_bwd_kernel(int n, const float* __restrict__ depth, const float* __restrict__ lidar, const float* __restrict__ mask,
 	int inv_depth, const double* __restrict__ work, const float* __restrict__ g_loss, float* __restrict__ out) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const double sm = work[2 * AUX_SLOTS + 1];
+	const double sm = work[AUX_TOTALS + 1];
 	const float m = mask[i];
 	double r;
 	float g = 0.f;
 	if (lidar_residual(depth[i], lidar[i], m, inv_depth, r) && sm > 0.0)
-		g = g_loss[0] * m * (r > 0.0 ? 1.f : (r < 0.0 ? -1.f : 0.f)) * (float)(1.0 / sm);
+		g = g_loss[0] * m * sgn(r) * (float)(1.0 / sm);
 	out[i] = g;
 }
 
@@ -520,7 +459,7 @@ using namespace adgs;
 // (adgs.loss._GroupVar) validates every new index tensor once and raises IndexError like the reference.
 constexpr int GV_MAXK = 32;
 __device__ __forceinline__ long long gv_row(long long i, int N) { if (i < 0) i += N; return (i < 0 || i >= N) ? -1 : i; }
-__global__ void __launch_bounds__(256) group_var_sum_kernel(int N, int G, int K, int D, const float* __restrict__ x, const long long* __restrict__ idx,
+__global__ void __launch_bounds__(SLOT_THREADS) group_var_sum_kernel(int N, int G, int K, int D, const float* __restrict__ x, const long long* __restrict__ idx,
 	double denom, double* __restrict__ work) {
 	const long long total = (long long)G * D;
 	double sum = 0;
@@ -533,9 +472,8 @@ __global__ void __launch_bounds__(256) group_var_sum_kernel(int N, int G, int K,
 		for (int k = 0; k < K; k++) { const float c = v[k] - mean; ss += c * c; }
 		sum += (double)(ss / (float)(K - 1));
 	}
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2, sum);
+	double v[1] = { sum };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 	if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(work + 1, denom);      // the "count" of the shared finish kernel
 }
 __global__ void __launch_bounds__(256) group_var_bwd_kernel(int N, int G, int K, int D, const float* __restrict__ x, const long long* __restrict__ idx,
@@ -552,15 +490,14 @@ __global__ void __launch_bounds__(256) group_var_bwd_kernel(int N, int G, int K,
 	if (!valid) return;          // a group with an out-of-range index has no defined variance: its rows receive NO gradient (never NaN) -- the forward's loss is NaN
 	for (int k = 0; k < K; k++) atomicAdd(dx + (size_t)row[k] * D + d, c * (v[k] - mean));
 }
-__global__ void __launch_bounds__(256) sigma_loss_sum_kernel(int N, const float* __restrict__ ls, float gap, double* __restrict__ work) {
+__global__ void __launch_bounds__(SLOT_THREADS) sigma_loss_sum_kernel(int N, const float* __restrict__ ls, float gap, double* __restrict__ work) {
 	double sum = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
 		const float m = 0.5f * (expf(ls[2 * i]) + expf(ls[2 * i + 1]));
 		sum += (double)fabsf(gap / m);
 	}
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(work + (size_t)((blockIdx.x * 4 + threadIdx.x / WAVE) % AUX_SLOTS) * 2, sum);
+	double v[1] = { sum };
+	slot_add_wave<ADGS_LOSS_SLOTS, AUX_ROW>(work, v);
 	if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(work + 1, (double)N);
 }
 __global__ void __launch_bounds__(256) sigma_loss_bwd_kernel(int N, const float* __restrict__ ls, float gap, const float* __restrict__ g_loss, float* __restrict__ d) {
@@ -568,8 +505,7 @@ __global__ void __launch_bounds__(256) sigma_loss_bwd_kernel(int N, const float*
 	if (i >= N) return;
 	const float e0 = expf(ls[2 * i]), e1 = expf(ls[2 * i + 1]);
 	const float m = 0.5f * (e0 + e1), q = gap / m;
-	const float sgn = q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f);
-	const float c = -sgn * q / m * 0.5f * g_loss[0] / (float)N;          // d|q|/dm = -sgn q / m;  dm/ds_j = e_j / 2
+	const float c = -sgn(q) * q / m * 0.5f * g_loss[0] / (float)N;          // d|q|/dm = -sgn q / m;  dm/ds_j = e_j / 2
 	d[2 * i] = c * e0; d[2 * i + 1] = c * e1;
 }
 
@@ -577,11 +513,11 @@ extern "C" int adgs_depth_loss_forward(int n, const float* prediction, const flo
 	if (n <= 0) return 0;
 	if (!prediction || !target || !work || !loss) { set_error("adgs_depth_loss_forward: NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	const int blocks = std::min((n + 255) / 256, 2048);
-	hipLaunchKernelGGL(depth_sums_kernel, dim3(blocks), dim3(256), 0, stream, n, prediction, target, mask, work);
-	hipLaunchKernelGGL(depth_solve_kernel, dim3(1), dim3(256), 0, stream, work);
-	hipLaunchKernelGGL(depth_l1_kernel, dim3(blocks), dim3(256), 0, stream, n, prediction, target, mask, work);
-	hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	const unsigned blocks = reduce_blocks(n);
+	hipLaunchKernelGGL(depth_sums_kernel, dim3(blocks), dim3(SLOT_THREADS), 0, stream, n, prediction, target, mask, work);
+	hipLaunchKernelGGL(depth_solve_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work);
+	hipLaunchKernelGGL(depth_l1_kernel, dim3(blocks), dim3(SLOT_THREADS), 0, stream, n, prediction, target, mask, work);
+	hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -609,25 +545,15 @@ extern "C" int adgs_l1_ssim_forward(int planes, int H, int W, const float* image
 
 // means of the two sums of adgs_l1_ssim_forward: out2 = (sum |image - gt|, sum ssim_map) / n; the slot rows are consumed (zero afterwards)
 namespace {
-__global__ void __launch_bounds__(256) l1_ssim_finish_kernel(double* __restrict__ sums, double inv_n, float* __restrict__ out2) {
-	__shared__ double s[2][256 / WAVE];
-	double a = sums[(size_t)threadIdx.x * 2], b = sums[(size_t)threadIdx.x * 2 + 1];
-	sums[(size_t)threadIdx.x * 2] = 0.0; sums[(size_t)threadIdx.x * 2 + 1] = 0.0;
-#pragma unroll
-	for (int off = WAVE / 2; off > 0; off >>= 1) { a += __shfl_xor(a, off, WAVE); b += __shfl_xor(b, off, WAVE); }
-	if ((threadIdx.x & (WAVE - 1)) == 0) { s[0][threadIdx.x / WAVE] = a; s[1][threadIdx.x / WAVE] = b; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		double ta = 0, tb = 0;
-		for (int w = 0; w < 256 / WAVE; w++) { ta += s[0][w]; tb += s[1][w]; }
-		out2[0] = (float)(ta * inv_n); out2[1] = (float)(tb * inv_n);
-	}
+__global__ void __launch_bounds__(SLOT_THREADS) l1_ssim_finish_kernel(double* __restrict__ sums, double inv_n, float* __restrict__ out2) {
+	double t[2];
+	slot_finish<ADGS_LOSS_SLOTS, 2>(sums, t);
+	if (threadIdx.x == 0) { out2[0] = (float)(t[0] * inv_n); out2[1] = (float)(t[1] * inv_n); }
 }
 }
 extern "C" int adgs_l1_ssim_means(double* sums, long long n, float* out2, void* stream) {
 	if (!sums || !out2) { set_error("adgs_l1_ssim_means: NULL pointer"); return -1; }
-	static_assert(ADGS_LOSS_SLOTS == 256, "one thread per slot row");
-	hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, 1.0 / (double)std::max<long long>(n, 1), out2);
+	hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, (hipStream_t)stream, sums, 1.0 / (double)std::max<long long>(n, 1), out2);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -649,21 +575,12 @@ extern "C" int adgs_l1_ssim_backward(int planes, int H, int W, const float* imag
 // ---------------------------------------------------------------- the weighted forms (include/adgs_loss.h)
 namespace {
 // totals of the three sums -> work[3 * SLOTS ..] = (sum w |d|, sum w ssim, sum w); out2 = the first two over planes * sum w, 0 when sum w = 0
-__global__ void __launch_bounds__(256) l1_ssim_weighted_finish_kernel(double* __restrict__ work, double planes, float* __restrict__ out2) {
-	__shared__ double s[3][256 / WAVE];
-	double v[3];
-#pragma unroll
-	for (int q = 0; q < 3; q++) {
-		v[q] = work[(size_t)threadIdx.x * 3 + q];
-		work[(size_t)threadIdx.x * 3 + q] = 0.0;                       // consumed
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
-	}
-	__syncthreads();
+__global__ void __launch_bounds__(SLOT_THREADS) l1_ssim_weighted_finish_kernel(double* __restrict__ work, double planes, float* __restrict__ out2) {
+	double t[3];
+	slot_finish<ADGS_LOSS_SLOTS, 3>(work, t);
 	if (threadIdx.x == 0) {
 		double* tot = work + 3 * ADGS_LOSS_SLOTS;
-		for (int q = 0; q < 3; q++) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[q][w]; tot[q] = t; }
+		for (int q = 0; q < 3; q++) tot[q] = t[q];
 		const double n = planes * tot[2];
 		out2[0] = tot[2] > 0 ? (float)(tot[0] / n) : 0.f; out2[1] = tot[2] > 0 ? (float)(tot[1] / n) : 0.f;
 	}
@@ -675,11 +592,11 @@ extern "C" int adgs_l1_ssim_weighted_forward(int planes, int H, int W, const flo
 	if (!image || !gt || !weight || !work || !out2) { set_error("adgs_l1_ssim_weighted_forward: NULL image / gt / weight / work / out2"); return -1; }
 	if ((d_mu1 != nullptr) != (d_e11 != nullptr) || (d_mu1 != nullptr) != (d_e12 != nullptr)) { set_error("adgs_l1_ssim_weighted_forward: pass all three derivative maps or none"); return -1; }
 	if (planes > 65535) { set_error("adgs_l1_ssim_weighted_forward: more than 65535 planes"); return -1; }
-	static_assert(ADGS_LOSS_SLOTS == 256 && ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES >= 3 * ADGS_LOSS_SLOTS + 3, "one thread per slot row; three totals behind the rows");
+	static_assert(ADGS_L1_SSIM_WEIGHTED_WORK_DOUBLES >= 3 * ADGS_LOSS_SLOTS + 3, "three totals behind the rows");
 	static const Window win = make_window();
 	const dim3 grid((W + TSX - 1) / TSX, (H + TSY - 1) / TSY, planes);
 	hipLaunchKernelGGL(l1_ssim_fwd_kernel<true>, grid, dim3(LT), 0, (hipStream_t)stream, H, W, image, gt, weight, win, work, d_mu1, d_e11, d_e12);
-	hipLaunchKernelGGL(l1_ssim_weighted_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, (double)planes, out2);
+	hipLaunchKernelGGL(l1_ssim_weighted_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, (hipStream_t)stream, work, (double)planes, out2);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -700,8 +617,8 @@ extern "C" int adgs_bce_clip_weighted_forward(int n, const float* pred, const fl
 	if (n <= 0) return 0;
 	if (!pred || !target || !weight || !work || !loss) { set_error("adgs_bce_clip_weighted_forward: NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	hipLaunchKernelGGL(bce_clip_weighted_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, n, pred, target, weight, lo, hi, invert, positive_target, work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(bce_clip_weighted_sum_kernel, dim3(reduce_blocks(n)), dim3(SLOT_THREADS), 0, stream, n, pred, target, weight, lo, hi, invert, positive_target, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -719,8 +636,8 @@ extern "C" int adgs_lidar_depth_loss_forward(int n, const float* depth, const fl
 	if (n <= 0) return 0;
 	if (!depth || !lidar_depth || !lidar_mask || !work || !loss) { set_error("adgs_lidar_depth_loss_forward: NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	hipLaunchKernelGGL(lidar_depth_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, n, depth, lidar_depth, lidar_mask, inv_depth, work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(lidar_depth_sum_kernel, dim3(reduce_blocks(n)), dim3(SLOT_THREADS), 0, stream, n, depth, lidar_depth, lidar_mask, inv_depth, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -750,8 +667,8 @@ static int flow_loss_forward_impl(const char* who, bool dev_cam, int H, int W, c
 	const int n = H * W;
 	FlowCam c; FlowCamDev cd{nullptr, nullptr, nullptr};
 	if (dev_cam) { c = FlowCam{}; c.dist = dist; cd = FlowCamDev{K, R, T}; } else c = make_flow_cam(K, R, T, dist);
-	hipLaunchKernelGGL(flow_loss_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, H, W, img_flow, flow, flow_vis, img_opacity, c, cd, work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(flow_loss_sum_kernel, dim3(reduce_blocks(n)), dim3(SLOT_THREADS), 0, stream, H, W, img_flow, flow, flow_vis, img_opacity, c, cd, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -793,8 +710,8 @@ extern "C" int adgs_bce_clip_forward(int n, const float* pred, const float* targ
 	if (n <= 0) return 0;
 	if (!pred || !target || !work || !loss) { set_error("adgs_bce_clip_forward: NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	hipLaunchKernelGGL(bce_clip_sum_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, stream, n, pred, target, lo, hi, invert, positive_target, work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(bce_clip_sum_kernel, dim3(reduce_blocks(n)), dim3(SLOT_THREADS), 0, stream, n, pred, target, lo, hi, invert, positive_target, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -812,9 +729,9 @@ extern "C" int adgs_group_var_forward(int N, int G, int K, int D, int inner, con
 	if (K < 2 || K > GV_MAXK || inner <= 0 || D % inner != 0 || N <= 0) { set_error("adgs_group_var_forward: needs 2 <= K <= 32 neighbours and D a multiple of inner"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
 	const long long total = (long long)G * D;
-	hipLaunchKernelGGL(group_var_sum_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, stream, N, G, K, D, x,
+	hipLaunchKernelGGL(group_var_sum_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(SLOT_THREADS), 0, stream, N, G, K, D, x,
 		reinterpret_cast<const long long*>(idx), (double)G * (double)(D / inner), work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -833,8 +750,8 @@ extern "C" int adgs_sigma_loss_forward(int N, const float* log_sigma, float fram
 	if (N <= 0) return 0;
 	if (!log_sigma || !work || !loss) { set_error("adgs_sigma_loss_forward: NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
-	hipLaunchKernelGGL(sigma_loss_sum_kernel, dim3(std::min((N + 255) / 256, 2048)), dim3(256), 0, stream, N, log_sigma, frame_gap, work);
-	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(sigma_loss_sum_kernel, dim3(reduce_blocks(N)), dim3(SLOT_THREADS), 0, stream, N, log_sigma, frame_gap, work);
+	hipLaunchKernelGGL(aux_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

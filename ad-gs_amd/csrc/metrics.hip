@@ -7,6 +7,7 @@
 // and its channels meet in an LDS byte tile from which the 8-bit rows leave as 32-bit words.
 #include "common.h"
 #include "ssim_window.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_metrics.h"
 
 namespace adgs {
@@ -134,8 +135,7 @@ __global__ void __launch_bounds__(LT) metrics_kernel(int C, int H, int W, int re
 		}
 #pragma unroll
 		for (int q = 0; q < NQ; q++) {
-#pragma unroll
-			for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
+			wave_sum(v[q]);
 			if ((tid & (WAVE - 1)) == 0) red[r][q][tid / WAVE] = v[q];
 		}
 	}
@@ -178,8 +178,7 @@ __global__ void __launch_bounds__(LT) metrics_finish_kernel(int nreg, double* __
 	for (int q = 0; q < NQ; q++) {
 		double v = p[q];
 		p[q] = 0.0;
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+		wave_sum(v);
 		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v;
 	}
 	__syncthreads();

@@ -10,8 +10,8 @@
 // (O >= min_opacity and D > 0) are staged ONCE per workgroup with their halo in LDS; z is formed and kept in double (its inputs are exact
 // floats, so the central differences of z carry no rounding of z itself -- at 1920 columns the float32 evaluation is not good to 1e-4), and
 // the per-pixel arithmetic behind it is double as well: the pass is bound by its six float reads per pixel, not by arithmetic.
-// Forward: halo 1; the sums (sum v e, sum v) go in double per thread, per wave (__shfl_xor), then into slot row
-// (block * 4 + wave) % ADGS_LOSS_SLOTS; the one-block finish kernel adds the rows up, leaves them zero and stores the totals and L.
+// Forward: halo 1; the sums (sum v e, sum v) go in double per thread, then through the slot rows (slot_reduce.h); the finish kernel stores
+// the totals and L behind the rows.
 // Backward: a gather with halo 2.  Phase 1: every staged pixel p of the tile plus a halo of 1 that is valid forms its depth normal once,
 // writes dL/dN(p) when it lies in the tile, and stores the gradients of its two tangents g_tx(p), g_ty(p) in LDS (float).  Phase 2: a tile
 // pixel q collects  r(q) . (g_tx(q - e_x) - g_tx(q + e_x) + g_ty(q - e_y) - g_ty(q + e_y))  -- t_x(p) = z(p + e_x) r(p + e_x) - z(p - e_x) r(p - e_x) --
@@ -20,6 +20,7 @@
 // Byte model (HBM): forward reads (5 + [weight]) * 4 * H * W bytes and writes the slot rows; backward reads the same and writes up to 5 * 4 * H * W.
 #include "common.h"
 #include "stream_access.h"
+#include "slot_reduce.h"
 #include "../../include/adgs_loss.h"
 #include "../../include/adgs_normals.h"
 #include <climits>
@@ -134,7 +135,7 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 constexpr int NC_TX = 32, NC_TY = 16, NC_LT = 256;
 constexpr int NC_ROW = 2;                                       // doubles per slot row
 constexpr int NC_MAX_TILES = (1 << 24) - 1;                     // tiles * 256 threads must stay below 2^32
-static_assert(ADGS_LOSS_SLOTS == 256 && ADGS_NORMAL_WORK_DOUBLES >= ADGS_LOSS_SLOTS * NC_ROW + 3, "one finish thread per slot row; three scalars behind the rows");
+static_assert(NC_LT == SLOT_THREADS && ADGS_NORMAL_WORK_DOUBLES >= ADGS_LOSS_SLOTS * NC_ROW + 3, "slot_add_wave's workgroup; three scalars behind the rows");
 enum { NC_SVE = 0, NC_SV, NC_L };                              // the scalars behind the rows: sum v e, sum v, L
 
 struct NcView {
@@ -213,7 +214,7 @@ __global__ void __launch_bounds__(NC_LT) normal_consistency_fwd_kernel(NcView v,
 	nc_stage<1>(v, depth, opacity, x0, y0, tid, sz, sv);
 	const size_t plane = (size_t)v.H * v.W;
 	const int lx = tid & (NC_TX - 1), gx = x0 + lx;
-	double acc_e = 0.0, acc_v = 0.0;
+	double acc[NC_ROW] = { 0.0, 0.0 };                          // sum v e, sum v
 #pragma unroll
 	for (int o = 0; o < 2; o++) {
 		const int ly = 2 * (tid >> 5) + o, gy = y0 + ly;
@@ -233,37 +234,21 @@ __global__ void __launch_bounds__(NC_LT) normal_consistency_fwd_kernel(NcView v,
 			const double n0 = normal[p], n1 = normal[plane + p], n2 = normal[2 * plane + p];
 			const double rho = sqrt(n0 * n0 + n1 * n1 + n2 * n2 + 1e-12);
 			const double e = 1.0 - (n0 * nd[0] + n1 * nd[1] + n2 * nd[2]) / rho;
-			acc_e += w * e; acc_v += w;
+			acc[NC_SVE] += w * e; acc[NC_SV] += w;
 		} else {
 			out[p] = (float)nd[0]; out[plane + p] = (float)nd[1]; out[2 * plane + p] = (float)nd[2];
 		}
 	}
-	if constexpr (LOSS) {
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) { acc_e += __shfl_xor(acc_e, off, WAVE); acc_v += __shfl_xor(acc_v, off, WAVE); }
-		if ((tid & (WAVE - 1)) == 0) {
-			double* row = work + (size_t)((blockIdx.x * 4u + (unsigned)(tid / WAVE)) % ADGS_LOSS_SLOTS) * NC_ROW;
-			atomicAdd(row, acc_e); atomicAdd(row + 1, acc_v);
-		}
-	}
+	if constexpr (LOSS) slot_add_wave<ADGS_LOSS_SLOTS, NC_ROW>(work, acc);
 }
 
 // one block: totals of the slot rows (left zero) -> the scalars behind them and the loss
-__global__ void __launch_bounds__(256) normal_consistency_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
-	__shared__ double s[NC_ROW][256 / WAVE];
-	double v[NC_ROW];
-#pragma unroll
-	for (int q = 0; q < NC_ROW; q++) {
-		v[q] = work[(size_t)threadIdx.x * NC_ROW + q];
-		work[(size_t)threadIdx.x * NC_ROW + q] = 0.0;              // consumed
-#pragma unroll
-		for (int off = WAVE / 2; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, WAVE);
-		if ((threadIdx.x & (WAVE - 1)) == 0) s[q][threadIdx.x / WAVE] = v[q];
-	}
-	__syncthreads();
+__global__ void __launch_bounds__(SLOT_THREADS) normal_consistency_finish_kernel(double* __restrict__ work, float* __restrict__ loss) {
+	double t[NC_ROW];
+	slot_finish<ADGS_LOSS_SLOTS, NC_ROW>(work, t);
 	if (threadIdx.x == 0) {
 		double* tot = work + (size_t)ADGS_LOSS_SLOTS * NC_ROW;
-		for (int q = 0; q < NC_ROW; q++) { double t = 0; for (int w = 0; w < 256 / WAVE; w++) t += s[q][w]; tot[q] = t; }
+		for (int q = 0; q < NC_ROW; q++) tot[q] = t[q];
 		const double L = tot[NC_SV] > 0.0 ? tot[NC_SVE] / tot[NC_SV] : 0.0;
 		tot[NC_L] = L;
 		loss[0] = (float)L;
@@ -400,7 +385,7 @@ extern "C" int adgs_normal_consistency_forward(int H, int W, const float* normal
 	hipStream_t stream = (hipStream_t)stream_;
 	const int tiles_x = (W + NC_TX - 1) / NC_TX;
 	hipLaunchKernelGGL(normal_consistency_fwd_kernel<true>, dim3((unsigned)tiles), dim3(NC_LT), 0, stream, v, tiles_x, normal, depth, opacity, weight, work, (float*)nullptr);
-	hipLaunchKernelGGL(normal_consistency_finish_kernel, dim3(1), dim3(256), 0, stream, work, loss);
+	hipLaunchKernelGGL(normal_consistency_finish_kernel, dim3(1), dim3(SLOT_THREADS), 0, stream, work, loss);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

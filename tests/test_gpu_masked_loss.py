@@ -153,8 +153,9 @@ def test_no_weight_is_bitwise_the_call_without_the_argument():
         assert torch.equal(a, b) and torch.equal(pa.grad, pb.grad)
 
 
-@pytest.mark.parametrize("shape", [(1, 3, 5), (3, 17, 33), (3, 37, 121), (2, 3, 17, 33)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", [(1, 3, 5), (3, 17, 33), (3, 37, 121), (2, 3, 17, 33), (3, 97, 481)], ids=lambda s: "x".join(map(str, s)))
 def test_weight_of_ones_against_the_unweighted_path(shape):
+    """3x97x481: 336 workgroups, the slot wrap of the unweighted kernel (the weighted one meets its reference there, above)"""
     from adgs import loss
     img, gt = images(shape)
     y = gt.cuda()
@@ -185,12 +186,17 @@ def test_training_loss_over_a_region_is_the_evaluators_metric_over_it(C):
         np.testing.assert_allclose(float(s), region["ssim"][0], rtol=1e-5)
 
 
-@pytest.mark.parametrize("kind", WEIGHTS)
-@pytest.mark.parametrize("term", ["obj", "sky"])
-def test_weighted_bce_terms(term, kind):
-    """both parameter sets, predictions drawn away from the clip bounds; the tolerances of tests/test_gpu_loss.py:136-139"""
+# the ids of the 37 x 121 cases are "term-kind", as they were before the second shape
+BCE_CASES = [pytest.param(term, kind, H, W, id="-".join((term, kind) + (("%dx%d" % (H, W),) if (H, W) != (37, 121) else ())))
+             for H, W in ((37, 121), (130, 127)) for kind in WEIGHTS for term in ("obj", "sky")]
+
+
+@pytest.mark.parametrize("term,kind,H,W", BCE_CASES)
+def test_weighted_bce_terms(term, kind, H, W):
+    """both parameter sets, predictions drawn away from the clip bounds; the tolerances of tests/test_gpu_loss.py:136-139.
+    37 x 121: 18 workgroups, one add per slot row; 130 x 127 = 16 510 elements: 65 workgroups of four waves, 260 adds into the 256 rows
+    (rows 0 - 3 take two each: a + b onto +0.0 in either order is the same double, so the result is still the same from every call)."""
     from adgs import loss
-    H, W = 37, 121
     g = torch.Generator().manual_seed(21)
     pred = torch.rand(H, W, generator=g) * 0.9 + 0.05
     tgt = (torch.rand(H, W, generator=g) > 0.6).float() * (3.0 if term == "obj" else 1.0)      # gt_semantic holds object ids: (> 0) is the target
@@ -206,6 +212,8 @@ def test_weighted_bce_terms(term, kind):
     assert not p.grad[w.cuda() == 0].any()
     direct = loss.bce_clip_loss(pred.cuda(), tgt.cuda(), *params, weight=w.cuda())
     assert torch.equal(direct, val.detach())
+    if kind == "ones":                                         # the kernel without a weight, against the same reference
+        np.testing.assert_allclose(float(loss.bce_clip_loss(pred.cuda(), tgt.cuda(), *params)), want, rtol=1e-5)
 
 
 @pytest.mark.parametrize("H,W,D_S", [(17, 33, 1), (37, 121, 2)])
@@ -268,8 +276,9 @@ def lidar_case(H, W, valid_fraction=0.02, seed=0):
 
 @pytest.mark.parametrize("mask_dtype", ["bool", "float"])
 @pytest.mark.parametrize("inv_depth", [False, True])
-@pytest.mark.parametrize("H,W", [(3, 5), (37, 121)])
+@pytest.mark.parametrize("H,W", [(3, 5), (37, 121), (130, 127)])
 def test_lidar_depth_loss(H, W, inv_depth, mask_dtype):
+    """130 x 127: 65 workgroups, more waves than slot rows"""
     from adgs import loss
     depth, lidar, mask = lidar_case(H, W)
     if inv_depth:

@@ -29,6 +29,7 @@ from tests import metrics_ref as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(3, 1, 1), (3, 5, 70), (3, 16, 32), (3, 17, 33), (3, 37, 53), (1, 40, 24), (3, 48, 200)]
+WRAP = (3, 17, 4097)                      # 129 x 2 = 258 tiles, the fewest over the 256 slot rows with partial tiles on both axes; not in the golden file
 GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "metrics_golden.npz"))
 L1_TOL, SSIM_TOL, PSNR_TOL = 1e-6, 1e-5, 1e-5
 MSE_REL = PSNR_TOL * math.log(10.0) / 10.0
@@ -42,6 +43,10 @@ def name_of(shape):
 @functools.lru_cache(maxsize=None)
 def inputs(shape):
     n = name_of(shape)
+    if shape == WRAP:                     # the golden file's recipe (tests/golden/make_metrics_golden.py)
+        g = torch.Generator().manual_seed(sum(shape))
+        gt = torch.rand(*shape, generator=g)
+        return gt + 0.15 * torch.randn(*shape, generator=g), gt
     return torch.from_numpy(GOLDEN[n + "/img"]), torch.from_numpy(GOLDEN[n + "/gt"])
 
 
@@ -86,7 +91,7 @@ def check_region(tag, got, want, view=0):
 
 
 @pytest.mark.parametrize("regions", [0, 1, 4])
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + [WRAP])
 def test_metrics_against_the_reference(shape, regions):
     img, gt = inputs(shape)
     res, _, ev = evaluate(img, gt, masks_of(shape, regions) if regions else None)
