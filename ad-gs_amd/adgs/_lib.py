@@ -150,6 +150,9 @@ SIGNATURES = {
     "adgs_normal_consistency_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p, c_p]),
     "adgs_normal_consistency_backward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_depth_to_normal": (c_i, [c_i, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p]),
+    # include/adgs_multiview.h
+    "adgs_multiview_ncc_forward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_multiview_ncc_backward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
