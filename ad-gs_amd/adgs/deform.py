@@ -143,6 +143,13 @@ def _dp(t):
     return None if (t is None or t.numel() == 0) else t.data_ptr()
 
 
+def _upstream(g):
+    """An upstream gradient as the backward kernels read it: contiguous fp32 at a 16-byte aligned address (the object range reads
+    its rotation rows as 16-byte words whatever the pointer; autograd's own tensors are aligned, a caller's view need not be)."""
+    g = g.contiguous().float()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
+
+
 class _FuncEvalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, param, feval):
@@ -201,6 +208,8 @@ class _DeformPkgFn(torch.autograd.Function):
         M = 1 + named["scene_shs_rest"].shape[1]
         p = DeformParams()
         p.Ns, p.No, p.sh_coeffs, p.use_time_mask, p.t = Ns, No, M, int(bool(use_time_mask)) | (2 if skip_scene else 0), float(t)      # bit 1: ADGS_DEFORM_SKIP_SCENE
+        if len(meta) > 7 and meta[7]:
+            p.use_time_mask |= 4          # ADGS_DEFORM_WILL_BACKWARD: refuse now what the backward could not stage, not in the middle of autograd
         for n in _PTRS:
             setattr(p, n, _dp(named[n]))
         # n_params is the parameter tensor's last dimension even when it has no rows (a model without object Gaussians)
@@ -248,8 +257,8 @@ class _DeformPkgFn(torch.autograd.Function):
             setattr(p, n, _dp(named[n]))
         up = {}
         for k, g in (("xyz", g_xyz), ("rotation", g_rot), ("shs", g_shs), ("opacity", g_op), ("scales", g_sc)):
-            up[k] = g.contiguous().float() if (k in want and g is not None and g.numel() > 0) else None
-        up["flow"] = g_flow.contiguous().float() if (flow_t is not None and g_flow is not None and g_flow.numel() > 0) else None
+            up[k] = _upstream(g) if (k in want and g is not None and g.numel() > 0) else None
+        up["flow"] = _upstream(g_flow) if (flow_t is not None and g_flow is not None and g_flow.numel() > 0) else None
         # which output each raw parameter feeds; a parameter whose output has no upstream gradient gets
         # no gradient tensor at all, the others are fully written by the kernels (no zero fill) except
         # the atomically accumulated background row
@@ -322,7 +331,8 @@ def get_deformed_pkg(model, t, want=("xyz", "rotation", "shs", "opacity", "scale
         return out
     tensors = [getattr(model, _MODEL_ATTRS[n], None) for n in _PTRS]
     meta = (float(t), dict(model.order_args), bool(getattr(model, "use_time_mask", False)), tuple(want),
-            None if flow_time is None else float(flow_time), getattr(model, "grad_arena", None), raw_scene == "objects_only")
+            None if flow_time is None else float(flow_time), getattr(model, "grad_arena", None), raw_scene == "objects_only",
+            torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in tensors))      # a backward will follow
     xyz, rot, shs, op, sc, flow = _DeformPkgFn.apply(meta, *tensors)
     out = {}
     if flow_time is not None:

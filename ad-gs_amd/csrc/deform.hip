@@ -337,8 +337,9 @@ __device__ __forceinline__ void deform_fwd_body(const DeformArgs& a, int blk, in
 		if (valid) {
 			float u[4];
 			if (!OBJ || !is_obj) {
-				const float4 q = *reinterpret_cast<const float4*>(a.p.scene_rotation + 4 * (size_t)m);
-				u[0] = q.x; u[1] = q.y; u[2] = q.z; u[3] = q.w;
+				// four 4-byte loads: this body serves the scene range exactly when scene4_ok found a pointer that is not 16-byte aligned
+				const float* q = a.p.scene_rotation + 4 * (size_t)m;
+				u[0] = q[0]; u[1] = q[1]; u[2] = q[2]; u[3] = q[3];
 			} else {
 				const float* rp = a.p.rotation_deform_param ? s_rows + tid * a.stride_r : nullptr;
 				float fv[4] = { 0.f, 0.f, 0.f, 0.f };
@@ -702,8 +703,8 @@ __device__ __forceinline__ void deform_bwd_body(const DeformBwdArgs& a, int blk,
 			QuatSave<(NQ > 0 ? NQ : 1)> qs;
 			Q qout = { 0.f, 0.f, 0.f, 0.f };
 			if (!OBJ || !is_obj) {
-				const float4 q = *reinterpret_cast<const float4*>(a.p.scene_rotation + 4 * (size_t)m);
-				u[0] = q.x; u[1] = q.y; u[2] = q.z; u[3] = q.w;
+				const float* q = a.p.scene_rotation + 4 * (size_t)m;      // 4-byte loads, as in the forward: the pointer may be misaligned
+				u[0] = q[0]; u[1] = q[1]; u[2] = q[2]; u[3] = q[3];
 			} else {
 				float fv[4] = { 0.f, 0.f, 0.f, 0.f };
 				if (rp) {
@@ -1017,6 +1018,15 @@ static int pick_block(int row_floats, size_t* lds) {
 	}
 	return 64;
 }
+// block size / LDS of the backward geometry launch: rows of the longer family, and behind the xyz gradient rows the dense basis
+// vectors of the two time stamps.  The forward asks too (ADGS_DEFORM_WILL_BACKWARD): it refuses what its backward could not stage.
+static int pick_block_bwd(int No, int np_x, int stride_x, int stride_r, size_t* lds) {
+	*lds = 0;
+	if (No <= 0) return 256;
+	const int B = pick_block(std::max(stride_x, stride_r), lds);
+	*lds = std::max(*lds, (size_t)B * stride_x * sizeof(float) + 2 * (size_t)np_x * sizeof(float));
+	return B;
+}
 
 int launch_sh0(int N, const ShSource& s, float* out, hipStream_t stream, const FramePrologue* prologue, int ostride) {
 	if (N <= 0) return 0;
@@ -1042,7 +1052,7 @@ int launch_sh0(int N, const ShSource& s, float* out, hipStream_t stream, const F
 	size_t lds = 0;
 	const int B = pick_block((3 * np) | 1, &lds);
 	if (lds > MAX_STAGING_LDS) { set_error("launch_sh0: SH deformation rows too large for the LDS staging buffer (more than 207 parameters per channel)"); return -1; }
-	if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sh0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	if (lds > 48 * 1024) ADGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sh0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	hipLaunchKernelGGL(sh0_kernel, dim3((unsigned)((N + B - 1) / B)), dim3(B), lds, stream, N, s, out, pro, ostride);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
@@ -1146,13 +1156,18 @@ extern "C" int adgs_deform_forward_flow(const adgs_deform_params* p, const adgs_
 			const int B = p->No > 0 ? pick_block(a.xyz_rows ? a.stride_r : std::max(a.stride_x, a.stride_r), &lds) : 256;
 			if (a.xyz_rows) lds = std::max(lds, (size_t)2 * np_x * sizeof(float));
 			if (lds > MAX_STAGING_LDS) { set_error("adgs_deform_forward: deformation rows too large for the LDS staging buffer"); return -1; }
+			if (p->use_time_mask & ADGS_DEFORM_WILL_BACKWARD) {
+				size_t lds_bwd = 0;
+				pick_block_bwd(p->No, np_x, a.stride_x, a.stride_r, &lds_bwd);
+				if (lds_bwd > MAX_STAGING_LDS) { set_error("adgs_deform_forward: deformation rows too large for the LDS staging buffer of the backward pass"); return -1; }
+			}
 			a.scene4 = scene4_ok({ p->scene_xyz, p->scene_rotation, p->scene_opacity, p->scene_scaling, a.o.xyz, a.flow_xyz, a.o.rotation, a.o.opacity, a.o.scales });
 			const int nb_o = (p->No + B - 1) / B, nb_scene = (p->use_time_mask & ADGS_DEFORM_SKIP_SCENE) ? 0 : (a.scene4 ? ((p->Ns + 3) / 4 + B - 1) / B : (p->Ns + B - 1) / B);
 			const int nb_rot = (a.o.rotation || a.o.opacity || a.o.scales) ? nb_o : 0;
 			const int nb_xyz = (a.o.xyz || a.flow_xyz) ? (a.xyz_rows ? (int)((3 * (size_t)p->No + B - 1) / B) : nb_o) : 0;
 			a.n_begin = 0; a.n_end = N;
 #define ADGS_CALL(NQ) do { if (nb_rot + nb_xyz + nb_scene == 0) break;      /* a model without objects on the raw-scene path: nothing to deform */ \
-				if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&deform_fwd_kernel<NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+				if (lds > 48 * 1024) ADGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&deform_fwd_kernel<NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
 				hipLaunchKernelGGL((deform_fwd_kernel<NQ>), dim3(nb_rot + nb_xyz + nb_scene), dim3(B), lds, stream, a, nb_rot, nb_xyz); } while (0)
 			ADGS_NQ_SWITCH(a.fr, ADGS_CALL)
 #undef ADGS_CALL
@@ -1209,11 +1224,7 @@ extern "C" int adgs_deform_backward_flow(const adgs_deform_params* p, const adgs
 		{
 			const bool want_rest = dL_dxyz || dL_dflow_xyz || dL_dopacity || dL_dscales;
 			size_t lds = 0;
-			int B = 256;
-			if (p->No > 0) {
-				B = pick_block(std::max(a.stride_x, a.stride_r), &lds);
-				lds = std::max(lds, (size_t)B * a.stride_x * sizeof(float) + 2 * (size_t)np_x * sizeof(float));     // + dense basis rows of the two time stamps
-			}
+			const int B = pick_block_bwd(p->No, np_x, a.stride_x, a.stride_r, &lds);
 			if (lds > MAX_STAGING_LDS) { set_error("adgs_deform_backward: deformation rows too large for the LDS staging buffer"); return -1; }
 			const int nb_o = (p->No + B - 1) / B;
 			a.scene4 = scene4_ok({ p->scene_xyz, p->scene_rotation, p->scene_opacity, p->scene_scaling, dL_dxyz, dL_dflow_xyz, dL_drotation, dL_dopacity, dL_dscales,
@@ -1221,7 +1232,7 @@ extern "C" int adgs_deform_backward_flow(const adgs_deform_params* p, const adgs
 			const int nb_rot = dL_drotation ? nb_o : 0, nb_xyz = want_rest ? nb_o : 0,
 				nb_scene = (p->use_time_mask & ADGS_DEFORM_SKIP_SCENE) ? 0 : (a.scene4 ? ((p->Ns + 3) / 4 + B - 1) / B : (p->Ns + B - 1) / B);
 			a.n_begin = 0; a.n_end = N;
-#define ADGS_CALL(NQ) do { if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&deform_bwd_kernel<NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+#define ADGS_CALL(NQ) do { if (lds > 48 * 1024) ADGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&deform_bwd_kernel<NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
 				if (nb_rot + nb_xyz + nb_scene != 0) hipLaunchKernelGGL((deform_bwd_kernel<NQ>), dim3(nb_rot + nb_xyz + nb_scene), dim3(B), lds, stream, a, nb_rot, nb_xyz); } while (0)
 			ADGS_NQ_SWITCH(a.fr, ADGS_CALL)
 #undef ADGS_CALL
