@@ -31,6 +31,27 @@ __device__ __forceinline__ void lin_bwd_add(float* __restrict__ grow, const adgs
 	for (int i = 0; i < total; i++) grow[f.index[i]] += f.weight[i] * g;
 }
 __device__ __forceinline__ bool has_lin(const adgs_func_eval& f) { return (f.n_terms[0] + f.n_terms[1] + f.n_terms[2]) > 0; }
+__device__ __forceinline__ int lin_terms(const adgs_func_eval& f) { return f.n_terms[0] + f.n_terms[1] + f.n_terms[2]; }
+
+// The dense basis vectors of two evaluations of the same parameter rows, assembled in LDS by the whole workgroup: s_w[k] = weight of
+// column k in f1 (its first t1 terms), s_w[np + k] the same for f2 (t2 terms); zero where there is no term.  Zero fill, barrier,
+// scatter, barrier.  UNIFORM: thread 0 scatters under a wave-uniform loop index -- for a kernel whose argument struct is a by-value
+// function parameter, which a per-lane index would move into scratch memory as a whole.
+// deform_lin_param_grad_kernel and sh0_rows_kernel fill their single vector with loops of their own: there the signedness of the
+// loop's stride decides whether the compiler keeps all of index[] / weight[] in registers, and in opposite directions (EXPERIMENTS.md).
+template <bool UNIFORM>
+__device__ __forceinline__ void scatter_basis(float* s_w, const adgs_func_eval& f, int terms, int tid, int nthreads) {
+	if (UNIFORM) { for (int i = 0; i < terms; i++) if (tid == 0) s_w[f.index[i]] = f.weight[i]; }
+	else for (int i = tid; i < terms; i += nthreads) s_w[f.index[i]] = f.weight[i];
+}
+template <bool UNIFORM = false>
+__device__ __forceinline__ void dense_basis_lds(float* s_w, int np, const adgs_func_eval& f1, int t1, const adgs_func_eval& f2, int t2, int tid, int nthreads) {
+	for (int k = tid; k < 2 * np; k += nthreads) s_w[k] = 0.f;
+	__syncthreads();
+	scatter_basis<UNIFORM>(s_w, f1, t1, tid, nthreads);
+	scatter_basis<UNIFORM>(s_w + np, f2, t2, tid, nthreads);
+	__syncthreads();
+}
 
 // Cooperative, fully coalesced transfer of the per-Gaussian parameter rows (L floats each) of the
 // `count` consecutive Gaussians gi0.. between global memory and LDS rows of `stride` floats (odd

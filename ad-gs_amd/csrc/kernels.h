@@ -225,7 +225,21 @@ int launch_render_sem_fwd_v2(const RenderV2SemFwdArgs& a, hipStream_t stream);
 // order_copy: the same permutation a second time (the camera's hint buffer), followed by the 16 floats of `view` (the pose the hint belongs to)
 int launch_tile_order(int ntiles, const uint32_t* tile_consumed, uint32_t* order, hipStream_t stream, uint32_t* order_copy = nullptr, const float* view = nullptr);
 
-// flat coalesced d/dparam[m, d, k] = w_k * g[m * gstride + d] for the linear families (deform.hip)
+// ---- deformation (deform.hip: geometry; deform_sh.hip: SH tensor, sh0, parameter-gradient rows) ----
+constexpr size_t MAX_STAGING_LDS = 156 * 1024;
+// block size / LDS of a kernel that stages one row of `row_floats` per thread (func_eval.h: stage_rows): the largest block whose rows fit
+// 48 KiB; one-wave blocks may take up to MAX_STAGING_LDS of the CU's 160 KiB (very long parameter rows: B-spline + polynomial + Fourier +
+// quaternion parts together)
+inline int pick_block(int row_floats, size_t* lds) {
+	int B = 256;
+	while (B > 64 && (size_t)B * row_floats * sizeof(float) > 48 * 1024) B >>= 1;
+	*lds = (size_t)B * row_floats * sizeof(float);
+	return B;
+}
+// the [N, sh_coeffs, 3] SH tensor of adgs_deform_forward / its gradient split into the raw tensors' gradients (+ the SH deformation rows')
+int launch_deform_shs_fwd(const adgs_deform_params& p, const adgs_func_eval& fs, float* shs_out, hipStream_t stream);
+int launch_deform_shs_bwd(const adgs_deform_params& p, const adgs_func_eval& fs, const float* dL_dshs, const adgs_deform_grads& grads, hipStream_t stream);
+// flat coalesced d/dparam[m, d, k] = w_k * g[m * gstride + d] for the linear families
 int launch_lin_param_grad(int count, int D, const float* g, int gstride, float* out, const adgs_func_eval& f, hipStream_t stream);
 // adam_a / adam_b (p != nullptr): the Adam step on that side's parameter rows in place of the store to out_a / out_b
 int launch_lin_param_grad2(int count_a, const float* g_a, float* out_a, int count_b, const float* g_b, float* out_b, int D, int gstride,

@@ -7,6 +7,7 @@
 #define ADGS_TESTING_H
 #include <stddef.h>
 #include <stdint.h>
+#include "adgs_deform.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -51,6 +52,18 @@ int adgs_test_scramble_slab_bounds(unsigned seed);
  * alone: 1 = grid columns staged / gradients accumulated in LDS, 0 = the footprint of a pixel tile can exceed the LDS budget (a small image
  * under a large grid): gathers from and atomics into global memory.  -1: a shape the entry points refuse. */
 int adgs_test_bilagrid_path(int L, int Hg, int Wg, int H, int W);
+
+/* The launch layout adgs_deform_forward_flow / adgs_deform_backward_flow (include/adgs_deform.h) would choose for their geometry kernel
+ * on these arguments, from the same two plan functions the entry points call.  Host only: no HIP call, no device needed, and no tensor
+ * pointer is dereferenced -- only the VALUES of the pointers in *p, *out, *grads and of the others are looked at (NULL or not,
+ * alignment).  np_*: n_params of f_xyz, f_xyz_flow and f_rotation.  fwd / bwd each receive ADGS_TEST_DEFORM_PLAN_FIELDS words:
+ * block size, dynamic LDS bytes, xyz row length, LDS stride of the xyz rows, of the rotation rows, xyz_rows (object xyz rows read
+ * directly), scene4 (scene range four Gaussians per thread), blocks of the rotation set, of the xyz set, of the scene set, and
+ * refused (0: no; 1: rows too large for the staging buffer; 2, forward with ADGS_DEFORM_WILL_BACKWARD: too large for the backward's). */
+#define ADGS_TEST_DEFORM_PLAN_FIELDS 11
+int adgs_test_deform_plan(const adgs_deform_params* p, int np_xyz, int np_xyz_flow, int np_rotation, const adgs_deform_outputs* out, const float* flow_xyz,
+	const float* dL_dxyz, const float* dL_drotation, const float* dL_dopacity, const float* dL_dscales, const float* dL_dflow_xyz,
+	const adgs_deform_grads* grads, int32_t* fwd, int32_t* bwd);
 
 #ifdef __cplusplus
 }

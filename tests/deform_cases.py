@@ -1,10 +1,12 @@
 """The case table of the deformation launch paths, shared by tests/test_deform_dispatch_ref.py (CPU) and
 tests/test_gpu_deform_dispatch.py (GPU).
 
-csrc/deform.hip's two launchers pick their kernels from the row lengths, the SH tensor shape, the quaternion-spline order and
-the pointer alignment.  Every case below is built for some of those decisions; `labels(case)` restates the launchers'
-predicates (pick_block, xyz_rows, scene4_ok, launch_sh0's `aligned`, ADGS_NQ_SWITCH) on the case's shapes, so the branch a
-case is meant to take is computed, not assumed, and REQUIRED_LABELS lists what the table must keep covering.
+The deformation entry points (csrc/deform.hip, csrc/deform_sh.hip) pick their kernels from the row lengths, the SH tensor shape,
+the quaternion-spline order and the pointer alignment.  Every case below is built for some of those decisions; `labels(case)`
+restates the predicates (plan_fwd / plan_bwd with pick_block and scene4_ok, launch_sh0's `aligned`, ADGS_NQ_SWITCH) on the case's
+shapes, so the branch a case is meant to take is computed, not assumed, and REQUIRED_LABELS lists what the table must keep
+covering.  `plan(case)` is compared with the library's own plan functions (adgs_test_deform_plan) in
+tests/test_deform_dispatch_ref.py.
 
 Two statements of the table's origin do not hold for the code as it is, and the mirror shows it:
   * an SH tensor with M = 4 has 12 floats per Gaussian, so N * M * 3 is always a multiple of 4 and deform_shs_fwd_kernel stores
@@ -17,8 +19,8 @@ import collections
 
 import numpy as np
 
-# ---- what the mirror restates of csrc/deform.hip
-MAX_STAGING_LDS = 156 * 1024          # deform.hip MAX_STAGING_LDS
+# ---- what the mirror restates of the library
+MAX_STAGING_LDS = 156 * 1024          # csrc/kernels.h MAX_STAGING_LDS
 LDS_OPT_IN = 48 * 1024                # above it a launch asks for hipFuncAttributeMaxDynamicSharedMemorySize first
 MAX_QUAT = 8                          # include/adgs_deform.h ADGS_FUNC_MAX_QUAT
 REFUSAL = "too large for the LDS staging buffer"
@@ -33,14 +35,15 @@ def get_param_num(oa):
 
 
 def pick_block(row_floats):
-    """deform.hip pick_block: the largest block whose rows fit 48 KiB, else one wave."""
+    """kernels.h pick_block: the largest block whose rows fit 48 KiB, else one wave."""
     for B in (256, 128, 64):
         if B * row_floats * 4 <= LDS_OPT_IN or B == 64:
             return B, B * row_floats * 4
 
 
 def plan(c):
-    """Block size and dynamic LDS of the forward and backward geometry launches, as the launchers compute them."""
+    """Block size, dynamic LDS, row path, scene path and refusal of the forward and backward geometry launches, as deform.hip's
+    plan_fwd / plan_bwd compute them."""
     np_x, np_r = get_param_num(c.xyz), get_param_num(c.rotation)
     sx, sr = (3 * np_x) | 1, (4 * np_r) | 1
     aligned = not c.misaligned
@@ -51,7 +54,8 @@ def plan(c):
     bB, blds = pick_block(max(sx, sr)) if c.No > 0 else (256, 0)
     if c.No > 0:
         blds = max(blds, bB * sx * 4 + 2 * np_x * 4)
-    return dict(np_x=np_x, np_r=np_r, xyz_rows=xyz_rows, fwd_B=fB, fwd_lds=flds, bwd_B=bB, bwd_lds=blds)
+    return dict(np_x=np_x, np_r=np_r, xyz_rows=xyz_rows, scene4=aligned, fwd_B=fB, fwd_lds=flds, bwd_B=bB, bwd_lds=blds,
+                fwd_refused=flds > MAX_STAGING_LDS, bwd_refused=blds > MAX_STAGING_LDS)
 
 
 def labels(c):
@@ -59,8 +63,7 @@ def labels(c):
     p = plan(c)
     out = set()
     N, np_s = c.Ns + c.No, get_param_num(c.shs)
-    fwd_refused = p["fwd_lds"] > MAX_STAGING_LDS
-    bwd_refused = p["bwd_lds"] > MAX_STAGING_LDS
+    fwd_refused, bwd_refused = p["fwd_refused"], p["bwd_refused"]
     if fwd_refused:
         return {"refuse_fwd"}
     if bwd_refused:

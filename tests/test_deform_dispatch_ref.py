@@ -71,12 +71,66 @@ def test_table_reaches_every_launch_path():
     assert dc.plan(by_id["xyz207_bwd_limit"])["fwd_lds"] == 158976
 
 
+def _library_plan(case):
+    """adgs_test_deform_plan on made-up addresses of the case's tensors: a tensor without elements is NULL, as adgs.deform passes it; the
+    model tensors of a misaligned twin lie one float behind a 16-byte boundary, outputs and gradients are aligned (fresh allocations)."""
+    import ctypes
+    from adgs import _lib, deform
+    lib = _lib.lib()
+    raw = dc.raw_inputs(case)
+    addr = iter(range(1 << 20, 1 << 30, 1 << 20))
+    fake = lambda n, off=0: (next(addr) + off) if n else None
+    p = deform.DeformParams()
+    p.Ns, p.No, p.sh_coeffs, p.t = case.Ns, case.No, case.M, case.t
+    p.use_time_mask = int(case.use_time_mask) | 4          # ADGS_DEFORM_WILL_BACKWARD
+    for name in dc.RAW_NAMES:
+        setattr(p, name, fake(raw[name].size, 4 if case.misaligned else 0))
+    N = case.Ns + case.No
+    out, grads = deform.DeformOutputs(), deform.DeformGrads()
+    for key in dc.OUTPUT_KEYS:
+        setattr(out, key, fake(N))
+    for name in dc.RAW_NAMES:
+        if name != "gs_time":
+            setattr(grads, name, fake(raw[name].size))
+    flow = fake(N if case.flow_time is not None else 0)
+    up = [fake(N) for _ in range(4)] + [fake(N if case.flow_time is not None else 0)]
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "adgs_testing.h")).read()
+    fields = int(re.search(r"#define ADGS_TEST_DEFORM_PLAN_FIELDS (\d+)", hdr).group(1))
+    fwd, bwd = (ctypes.c_int32 * fields)(), (ctypes.c_int32 * fields)()
+    np_x, np_r = dc.get_param_num(case.xyz), dc.get_param_num(case.rotation)
+    assert lib.adgs_test_deform_plan(ctypes.byref(p), np_x, np_x, np_r, ctypes.byref(out), flow, *up, ctypes.byref(grads), fwd, bwd) == 0
+    names = ("B", "lds", "np_x", "stride_x", "stride_r", "xyz_rows", "scene4", "nb_rot", "nb_xyz", "nb_scene", "refused")
+    assert len(names) == fields
+    return dict(zip(names, fwd)), dict(zip(names, bwd))
+
+
+@pytest.mark.parametrize("case", dc.CASES, ids=dc.IDS)
+def test_mirror_plan_equals_the_library_plan(case):
+    """The premise of the labels: `plan(case)` of the mirror is what deform.hip's plan_fwd / plan_bwd decide -- block size and dynamic LDS of
+    both launches, the direct-rows and four-per-thread scene paths, and who refuses (the forward for itself: 1, for its backward: 2)."""
+    fwd, bwd = _library_plan(case)
+    p = dc.plan(case)
+    assert (fwd["B"], fwd["lds"], bwd["B"], bwd["lds"]) == (p["fwd_B"], p["fwd_lds"], p["bwd_B"], p["bwd_lds"]), case.id
+    assert fwd["xyz_rows"] == int(p["xyz_rows"]) and bwd["xyz_rows"] == 0, case.id
+    assert fwd["scene4"] == bwd["scene4"] == int(p["scene4"]), case.id
+    assert (fwd["refused"] == 1) == p["fwd_refused"], case.id
+    assert (fwd["refused"] == 2) == (p["bwd_refused"] and not p["fwd_refused"]), case.id
+    assert (bwd["refused"] == 1) == p["bwd_refused"] and bwd["refused"] in (0, 1), case.id
+    for side in (fwd, bwd):
+        assert (side["np_x"], side["stride_x"], side["stride_r"]) == (p["np_x"], (3 * p["np_x"]) | 1, (4 * p["np_r"]) | 1), case.id
+    # the grid: the object range once per block set, the scene range in groups of four when scene4
+    nb_o = lambda B: -(-case.No // B)
+    nb_s = lambda B: -(-(-(-case.Ns // 4) if p["scene4"] else case.Ns) // B)
+    assert (fwd["nb_rot"], fwd["nb_scene"]) == (nb_o(fwd["B"]), nb_s(fwd["B"])), case.id
+    assert fwd["nb_xyz"] == (-(-3 * case.No // fwd["B"]) if p["xyz_rows"] else nb_o(fwd["B"])), case.id
+    assert (bwd["nb_rot"], bwd["nb_xyz"], bwd["nb_scene"]) == (nb_o(bwd["B"]), nb_o(bwd["B"]), nb_s(bwd["B"])), case.id
+
+
 def test_mirror_constants_match_the_kernel_source():
-    """The premise of the labels: the mirror uses deform.hip's own constants."""
+    """The constants the mirror shares with the sources, and the wording of the refusals."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "ad-gs_amd", "csrc", "deform.hip")).read()
+    csrc = lambda name: open(os.path.join(root, "ad-gs_amd", "csrc", name)).read()
     hdr = open(os.path.join(root, "include", "adgs_deform.h")).read()
-    assert int(re.search(r"constexpr size_t MAX_STAGING_LDS = (\d+) \* 1024;", src).group(1)) * 1024 == dc.MAX_STAGING_LDS
+    assert int(re.search(r"constexpr size_t MAX_STAGING_LDS = (\d+) \* 1024;", csrc("kernels.h")).group(1)) * 1024 == dc.MAX_STAGING_LDS
     assert int(re.search(r"#define ADGS_FUNC_MAX_QUAT (\d+)", hdr).group(1)) == dc.MAX_QUAT
-    assert "bytes <= 48 * 1024 || B == 64" in src and "for (int B = 256; B >= 64; B >>= 1)" in src
-    assert src.count(dc.REFUSAL) >= 3
+    assert csrc("deform.hip").count(dc.REFUSAL) + csrc("deform_sh.hip").count(dc.REFUSAL) >= 3
