@@ -15,6 +15,7 @@ One wave per sample and one tap per lane, forward in one launch plus the finish,
 [S, T] tensor exists.  There is no CPU fallback.
 """
 import ctypes
+import math
 
 import torch
 
@@ -214,3 +215,178 @@ def patch_errors(img_normal, depth, img_opacity, camera_or_tanfov, ref_gray, nbr
                   nbr.data_ptr(), _ptr(w), samples.data_ptr(), S, work.data_ptr(), loss.data_ptr(), e.data_ptr(), valid.data_ptr())
         token.done()
     return e, valid.bool()
+
+
+# ---- the geometric term (include/adgs_multiview_geo.h): the depth reprojection error between two renders ----
+#
+#     pkg, pkg_n = render(cam, model, None, pipe), render(nbr, model, None, pipe)      # the same time stamp
+#     L_geo = geometric_consistency_loss(pkg["depth"], pkg["img_opacity"], cam, pkg_n["depth"], pkg_n["img_opacity"], nbr, rel,
+#                                        weight=static_mask, inv_depth=pipe.inv_depth)
+#     err, geo_weight = reprojection_errors(...the same arguments...)                  # exp(-err) where the round trip closes, else 0
+#     idx = sample_pixels(static_mask * geo_weight, 102400, radius=3)
+#     L_ncc = photometric_consistency_loss(..., idx, weight=static_mask * geo_weight)
+
+MULTIVIEW_GEO_WORK_DOUBLES = 256 * 2 + 4    # ADGS_MULTIVIEW_GEO_WORK_DOUBLES
+
+
+class MultiviewGeoDesc(ctypes.Structure):
+    """adgs_multiview_geo_desc (include/adgs_multiview_geo.h)."""
+    _fields_ = [("struct_bytes", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Hn", ctypes.c_int), ("Wn", ctypes.c_int),
+                ("inv_depth", ctypes.c_int), ("tanfovx", ctypes.c_float), ("tanfovy", ctypes.c_float), ("tanfovx_n", ctypes.c_float),
+                ("tanfovy_n", ctypes.c_float), ("min_opacity", ctypes.c_float), ("max_pixel_error", ctypes.c_float), ("pose", ctypes.c_float * 12)]
+
+
+def make_geo_desc(H, W, Hn, Wn, inv_depth, tan, tan_n, min_opacity, max_pixel_error, pose):
+    """An adgs_multiview_geo_desc; pose: 12 numbers, R row-major then t."""
+    return MultiviewGeoDesc(ctypes.sizeof(MultiviewGeoDesc), H, W, Hn, Wn, int(bool(inv_depth)), tan[0], tan[1], tan_n[0], tan_n[1], min_opacity,
+                            max_pixel_error, (ctypes.c_float * 12)(*pose))
+
+
+def _pose12(pose, who):
+    if not torch.is_tensor(pose):
+        raise TypeError("%s: pose must be a tensor (relative_pose), got %s" % (who, type(pose).__name__))
+    if tuple(pose.shape) != (3, 4) or not pose.dtype.is_floating_point:
+        raise ValueError("%s: pose must be a floating-point [3, 4] tensor (R | t), got %s %s" % (who, pose.dtype, tuple(pose.shape)))
+    if pose.device.type != "cpu":
+        raise RuntimeError("%s: pose must be a host tensor (relative_pose), it is on %s" % (who, pose.device))
+    p = pose.detach().to(torch.float64)
+    pose12 = p[:, :3].reshape(-1).tolist() + p[:, 3].tolist()
+    if not all(abs(x) < float("inf") for x in pose12):
+        raise ValueError("%s: pose must be finite" % who)
+    return pose12
+
+
+def _prepare_geo(who, depth, img_opacity, camera_or_tanfov, nbr_depth, nbr_opacity, nbr_camera_or_tanfov, pose, weight, inv_depth, min_opacity,
+                 max_pixel_error):
+    """The checks both entries share -> (desc arguments, the weight): decided from the arguments alone, nothing is read back."""
+    _check_map(depth, "depth", None, None, None, who)
+    H, W = depth.shape[-2:]
+    device = depth.device
+    _check_map(img_opacity, "img_opacity", H, W, device, who)
+    tan = _tanfov(camera_or_tanfov, who)
+    _check_map(nbr_depth, "nbr_depth", None, None, device, who)
+    Hn, Wn = nbr_depth.shape[-2:]
+    _check_map(nbr_opacity, "nbr_opacity", Hn, Wn, device, who)
+    tan_n = _tanfov(nbr_camera_or_tanfov, who)
+    pose12 = _pose12(pose, who)
+    mo = _min_opacity(min_opacity, who)
+    me = float(max_pixel_error)
+    if not (0.0 < me < float("inf")):
+        raise ValueError("%s: max_pixel_error must be finite and > 0, got %r" % (who, max_pixel_error))
+    w = None if weight is None else _check_weight(weight, H, W, device, who)
+    if not depth.is_cuda:
+        raise RuntimeError("%s: tensors must be on a HIP device; there is no CPU path" % who)
+    return (H, W, Hn, Wn, bool(inv_depth), tan, tan_n, mo, me, pose12), w
+
+
+class _MultiviewGeo(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, opacity, nbr_depth, nbr_opacity, desc, w):
+        H, W, Hn, Wn = desc[:4]
+        d, o = depth.contiguous().reshape(H, W), opacity.contiguous().reshape(H, W)
+        dn, on = nbr_depth.contiguous().reshape(Hn, Wn), nbr_opacity.contiguous().reshape(Hn, Wn)
+        ctx.launched = bool(d.numel() and dn.numel())
+        ctx.desc, ctx.has_w = desc, w is not None
+        ctx.shapes = (depth.shape, opacity.shape, nbr_depth.shape, nbr_opacity.shape)
+        out = _scalar(d.device, ctx.launched)
+        work, ctx.token = _work(d.device, MULTIVIEW_GEO_WORK_DOUBLES)     # the backward reads sum w v from `work`
+        if ctx.launched:
+            _lib.call("adgs_multiview_geo_forward", d.device, ctypes.byref(make_geo_desc(*desc)), d.data_ptr(), o.data_ptr(), dn.data_ptr(), on.data_ptr(),
+                      _ptr(w), work.data_ptr(), out.data_ptr(), None, None)
+        ctx.token.done()
+        ctx.save_for_backward(d, o, dn, on, work, *([w] if w is not None else []))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        d, o, dn, on, work, *rest = ctx.saved_tensors
+        w = rest[0] if ctx.has_w else None
+        need = ctx.needs_input_grad[:4]
+        new = torch.empty_like if ctx.launched else torch.zeros_like      # the native call writes every element of what it is given
+        grads = [new(t) if n else None for t, n in zip((d, o, dn, on), need)]
+        gl = _g1(g_loss)
+        if ctx.launched and any(need):
+            _lib.call("adgs_multiview_geo_backward", d.device, ctypes.byref(make_geo_desc(*ctx.desc)), d.data_ptr(), o.data_ptr(), dn.data_ptr(),
+                      on.data_ptr(), _ptr(w), work.data_ptr(), gl.data_ptr(), *[_ptr(g) for g in grads])
+        return (*[None if g is None else g.reshape(s) for g, s in zip(grads, ctx.shapes)], None, None)
+
+
+def geometric_consistency_loss(depth, img_opacity, camera_or_tanfov, nbr_depth, nbr_opacity, nbr_camera_or_tanfov, pose, weight=None,
+                               inv_depth=True, min_opacity=0.5, max_pixel_error=1.0):
+    """The multi-view geometric consistency term (include/adgs_multiview_geo.h): every pixel of the reference view is lifted with the
+    rendered depth, projected into the neighbour, re-lifted with the depth the neighbour rendered there (bilinear) and projected back;
+    err is the distance in pixels between where it started and where it lands, and loss = sum w v exp(-err) err / sum w v with
+    exp(-err) a constant of the differentiation; 0 with zero gradients when no pixel is valid (decided on the device).
+
+    depth, img_opacity: float32 [H, W] or [1, H, W], as render() returns them (`inv_depth` = pipe.inv_depth); nbr_depth, nbr_opacity:
+    the same of the NEIGHBOUR'S OWN RENDER, [Hn, Wn] or [1, Hn, Wn] -- its own size and nbr_camera_or_tanfov; the cameras: FoVx / FoVy
+    or a (tanfovx, tanfovy) pair; pose: relative_pose(cam, nbr), a [3, 4] host tensor; weight: an optional [H, W] supervision weight
+    (see adgs.loss.l1_ssim), a constant.  A pixel is valid when O >= min_opacity and D > 0, it lands inside the neighbour's image in
+    front of its camera, the four corners it samples there have On >= min_opacity and Dn > 0, the re-lifted point is in front of the
+    reference camera, and err < max_pixel_error.  Gradients go to whichever of the four maps require them: the reference view's are
+    deterministic to the bit, the neighbour's are sums of float atomics.  Render the neighbour under torch.no_grad() to skip them."""
+    who = "geometric_consistency_loss"
+    desc, w = _prepare_geo(who, depth, img_opacity, camera_or_tanfov, nbr_depth, nbr_opacity, nbr_camera_or_tanfov, pose, weight, inv_depth,
+                           min_opacity, max_pixel_error)
+    return _MultiviewGeo.apply(depth, img_opacity, nbr_depth, nbr_opacity, desc, w)
+
+
+def reprojection_errors(depth, img_opacity, camera_or_tanfov, nbr_depth, nbr_opacity, nbr_camera_or_tanfov, pose, weight=None, inv_depth=True,
+                        min_opacity=0.5, max_pixel_error=1.0):
+    """(err [H, W], geo_weight [H, W]) float32 of the same arguments, forward only: err is the reprojection error in pixels wherever
+    every gate before the last holds (0 elsewhere); geo_weight = exp(-err) at the valid pixels (err < max_pixel_error included), 0
+    elsewhere.  geo_weight is what to multiply into the `weight=` of photometric_consistency_loss and to hand to sample_pixels: it keeps
+    occluded and inconsistent pixels out of the photometric term, as upstream does.  `weight` does not enter either map."""
+    who = "reprojection_errors"
+    desc, w = _prepare_geo(who, depth, img_opacity, camera_or_tanfov, nbr_depth, nbr_opacity, nbr_camera_or_tanfov, pose, weight, inv_depth,
+                           min_opacity, max_pixel_error)
+    H, W, Hn, Wn = desc[:4]
+    d, o = depth.detach().contiguous().reshape(H, W), img_opacity.detach().contiguous().reshape(H, W)
+    dn, on = nbr_depth.detach().contiguous().reshape(Hn, Wn), nbr_opacity.detach().contiguous().reshape(Hn, Wn)
+    launched = bool(d.numel() and dn.numel())
+    err, gw = ((torch.empty if launched else torch.zeros)((H, W), dtype=torch.float32, device=d.device) for _ in range(2))
+    if launched:
+        loss = _scalar(d.device, True)
+        work, token = _work(d.device, MULTIVIEW_GEO_WORK_DOUBLES)
+        _lib.call("adgs_multiview_geo_forward", d.device, ctypes.byref(make_geo_desc(*desc)), d.data_ptr(), o.data_ptr(), dn.data_ptr(), on.data_ptr(),
+                  _ptr(w), work.data_ptr(), loss.data_ptr(), err.data_ptr(), gw.data_ptr())
+        token.done()
+    return err, gw
+
+
+def nearest_cameras(cameras, k=1, max_angle=math.radians(30.0), min_distance=0.0, max_distance=1.5):
+    """For every camera of the sequence, the indices of up to `k` OTHER cameras to use as its neighbours: a list of lists of int.  A
+    candidate qualifies when the angle between the two viewing directions is <= max_angle (radians) and the distance between the two
+    centres lies in (min_distance, max_distance]; the qualifying ones are ordered by distance, then by index.  A driving rig moves
+    along its viewing direction, so the angle alone cannot rank neighbours; a stationary ego gives a zero baseline, which min_distance
+    excludes.  Directions and centres come from the `world_view_transform`s, read as relative_pose reads them (A = V.T maps world to
+    camera: the centre is -R^T t, the viewing direction the third row of R).  Host torch in float64; this READS THE MATRICES BACK from
+    the device: call it once, when the cameras are loaded."""
+    cameras = list(cameras)
+    k = int(k)
+    max_angle, min_distance, max_distance = float(max_angle), float(min_distance), float(max_distance)
+    if k < 0:
+        raise ValueError("nearest_cameras: k must be >= 0")
+    if not (0.0 <= max_angle <= math.pi) or not (0.0 <= min_distance <= max_distance < float("inf")):
+        raise ValueError("nearest_cameras: max_angle must lie in [0, pi] and 0 <= min_distance <= max_distance < inf")
+    centres, dirs = [], []
+    for i, cam in enumerate(cameras):
+        V = getattr(cam, "world_view_transform", cam)
+        if not torch.is_tensor(V) or tuple(V.shape) != (4, 4):
+            raise ValueError("nearest_cameras: cameras[%d] must be a camera with a [4, 4] world_view_transform (or that matrix)" % i)
+        A = V.detach().to("cpu", torch.float64).T
+        R, t = A[:3, :3], A[:3, 3]
+        centres.append(-R.T @ t)
+        dirs.append(R[2] / R[2].norm())
+    if not cameras:
+        return []
+    C, Z = torch.stack(centres), torch.stack(dirs)
+    dist = (C[:, None] - C[None]).norm(dim=-1)
+    angle = torch.acos((Z @ Z.T).clamp(-1.0, 1.0))
+    ok = (angle <= max_angle) & (dist > min_distance) & (dist <= max_distance)
+    ok.fill_diagonal_(False)
+    out = []
+    for i in range(len(cameras)):
+        cand = sorted((float(dist[i, j]), j) for j in ok[i].nonzero().reshape(-1).tolist())
+        out.append([j for _, j in cand[:k]])
+    return out
