@@ -156,6 +156,12 @@ SIGNATURES = {
     # include/adgs_multiview_geo.h
     "adgs_multiview_geo_forward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_multiview_geo_backward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_tsdf.h
+    "adgs_tsdf_integrate": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_tsdf_extract_temp_bytes": (ctypes.c_size_t, [c_p]),
+    "adgs_tsdf_extract_owner_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_tsdf_extract_count": (c_i, [c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+    "adgs_tsdf_extract_emit": (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

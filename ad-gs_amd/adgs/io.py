@@ -2,6 +2,7 @@
 write and read them (scene/gaussian_model.py:413-459, 465-541), so that models trained by either implementation load in the
 other.  The reference goes through the `plyfile` package (not installed here); the binary little-endian PLY it produces --
 one `vertex` element of float32 properties in construct_list_of_attributes order -- is written and parsed directly.
+write_mesh_ply / read_mesh_ply: the triangle mesh adgs.tsdf extracts, as a binary PLY with a face list.
 File I/O on the host; nothing here is on the per-frame path.
 """
 import os
@@ -72,6 +73,94 @@ def read_ply(path):
             data = np.frombuffer(f.read(count * rec.itemsize), dtype=rec, count=count)
             cols = {n: np.asarray(data[n]) for n, _ in props}
     return [n for n, _ in props], cols
+
+
+def write_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh as a binary little-endian PLY: `vertex` (float x, y, z and, with colours, uchar red, green, blue) and `face`
+    (list uchar int vertex_indices), the layout MeshLab, Blender and Open3D read.  vertices [V, 3], faces [F, 3], colors [V, 3] in
+    [0, 1] or None: tensors (any device) or arrays.  A colour becomes (255 * clip(c, 0, 1)) truncated to uint8, as the evaluation's
+    to8b does."""
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    v, f = np.ascontiguousarray(host(vertices), dtype='<f4'), host(faces)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("write_mesh_ply: vertices must be [V, 3], got %s" % (v.shape,))
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError("write_mesh_ply: faces must be an integer [F, 3] array, got %s %s" % (f.dtype, f.shape))
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("write_mesh_ply: faces must index the %d vertices" % v.shape[0])
+    props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % v.shape[0]
+    if colors is not None:
+        c = host(colors)
+        if c.shape != v.shape:
+            raise ValueError("write_mesh_ply: colors must be [V, 3] = %s, got %s" % (v.shape, c.shape))
+        props += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    vrec = np.empty(v.shape[0], dtype=np.dtype(props))
+    for a, n in enumerate("xyz"):
+        vrec[n] = v[:, a]
+    if colors is not None:
+        c8 = (255 * np.clip(c.astype(np.float32), 0, 1)).astype(np.uint8)
+        for a, n in enumerate(("red", "green", "blue")):
+            vrec[n] = c8[:, a]
+    frec = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    frec["n"] = 3
+    frec["v"] = f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_mesh_ply(path):
+    """A binary little-endian triangle-mesh PLY as write_mesh_ply writes it -> (vertices [V, 3] float32, faces [F, 3] int32,
+    colors [V, 3] uint8 or None), numpy arrays.  Extra scalar vertex properties are skipped; a face that is not a triangle is refused."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: unterminated PLY header" % path)
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError("%s: read_mesh_ply reads binary_little_endian files, this one is %s" % (path, fmt))
+        vertices = colors = None
+        faces = np.zeros((0, 3), np.int32)
+        for name, count, props in elements:
+            if name == "face":
+                if len(props) != 1 or props[0][0] != "list":
+                    raise ValueError("%s: the face element must be one list property" % path)
+                rec = np.dtype([("n", "<" + _PLY_TYPES[props[0][1]]), ("v", "<" + _PLY_TYPES[props[0][2]], (3,))])
+                data = np.frombuffer(f.read(count * rec.itemsize), dtype=rec, count=count)
+                if count and not (data["n"] == 3).all():
+                    raise ValueError("%s: every face must be a triangle" % path)
+                faces = np.ascontiguousarray(data["v"], dtype=np.int32)
+            else:
+                if any(p[0] == "list" for p in props):
+                    raise ValueError("%s: list properties are supported in the face element only" % path)
+                rec = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+                data = np.frombuffer(f.read(count * rec.itemsize), dtype=rec, count=count)
+                if name == "vertex":
+                    vertices = np.stack([data[n] for n in "xyz"], axis=1).astype(np.float32) if count else np.zeros((0, 3), np.float32)
+                    if all(n in rec.names for n in ("red", "green", "blue")):
+                        colors = np.stack([data[n] for n in ("red", "green", "blue")], axis=1).astype(np.uint8) if count else np.zeros((0, 3), np.uint8)
+    if vertices is None:
+        raise ValueError("%s has no vertex element" % path)
+    return vertices, faces, colors
 
 
 def save_ply(model, path):

@@ -1,0 +1,429 @@
+// TSDF fusion of rendered depth maps and marching tetrahedra on the fused volume, for gfx950 (wave64).
+// The definition is in include/adgs_tsdf.h.
+//
+// Integration: one thread per lattice point over the linear index, 256 per workgroup, so a wave touches 64 consecutive floats (256
+// contiguous bytes) of tsdf, wsum and each colour plane.  The position comes from (i, j, k) directly and the chain is double: the nearest
+// pixel is a floor() of a projected coordinate and the update is a gate on z_d - z, so a float32 chain would decide differently from the
+// definition at pixel boundaries and at the truncation band far more often than the handful of exact ties.  A point that fails a gate
+// returns before it reads the volume: the traffic of a view is 8 (+ 12 with colour) bytes read and as many written per UPDATED point,
+// plus the image pixels it gathers (neighbouring lattice points share them).
+//
+// Extraction: classify, scan, emit over chunks of 256 consecutive lattice points (one workgroup each), which gives the canonical order of
+// the header for free.  A lattice point owns its 7 forward edges (the vertices) and the cell it is the lowest corner of (the faces).
+//   count        per chunk: vertices, faces, "has a vertex"                            -> three uint32 per chunk
+//   scan         exclusive_scan_u32_sum over each of the three; the totals travel as 64-bit sums and are read back once
+//   emit points  recomputes the chunk; writes its vertices and, for chunks with vertices only, one word per owner:
+//                (offset of the owner's first vertex within the chunk) << 8 | its 7 slot bits
+//   emit faces   recomputes the chunk's cells; the id of a vertex on an edge is its owner's chunk base + the owner's offset + the
+//                popcount of the lower slot bits
+// A point whose 8 forward corners all have one sign owns no vertex and no face and costs 8 loads; otherwise the 27 wsum values around it
+// decide which of the 7 cells that contain its edges are valid.
+#include "common.h"
+#include "../../include/adgs_tsdf.h"
+#include <climits>
+#include <cmath>
+
+namespace adgs {
+namespace {
+
+constexpr int TSDF_THREADS = ADGS_TSDF_CHUNK;
+static_assert(TSDF_THREADS == 256 && ADGS_TSDF_OWNER_BYTES_PER_CHUNK == TSDF_THREADS * sizeof(uint32_t), "one word per owner of a chunk");
+
+struct Lattice {
+	int nx, ny, nz;
+	unsigned n;             // nx ny nz < 2^31
+	double vs, o[3];
+};
+
+struct TsdfView {
+	int H, W, inv_depth;
+	double kx, ky, cx, cy;  // W / (2 tanfovx), H / (2 tanfovy), (W - 1) / 2, (H - 1) / 2
+	double R[9], t[3];
+	double near, max_depth, trunc, max_weight;
+	float min_opacity;
+};
+
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(Lattice L, TsdfView v, const float* __restrict__ depth, const float* __restrict__ opacity,
+	const float* __restrict__ image, const float* __restrict__ weight, float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ color) {
+	const unsigned idx = blockIdx.x * (unsigned)TSDF_THREADS + threadIdx.x;
+	if (idx >= L.n) return;
+	const unsigned row = idx / (unsigned)L.nx;
+	const int i = (int)(idx - row * (unsigned)L.nx), k = (int)(row / (unsigned)L.ny), j = (int)(row - (unsigned)k * (unsigned)L.ny);
+	const double X0 = L.o[0] + L.vs * (double)i, X1 = L.o[1] + L.vs * (double)j, X2 = L.o[2] + L.vs * (double)k;
+	const double z = v.R[6] * X0 + v.R[7] * X1 + v.R[8] * X2 + v.t[2];
+	if (!(z > v.near)) return;
+	const double x = v.R[0] * X0 + v.R[1] * X1 + v.R[2] * X2 + v.t[0];
+	const double y = v.R[3] * X0 + v.R[4] * X1 + v.R[5] * X2 + v.t[1];
+	// A cull in front of the exact test, to spare most of the lattice the two divisions: with z > 0, u + 0.5 < -1 and u + 0.5 > W + 1 are
+	// x kx < -(cx + 1.5) z and x kx > (W + 0.5 - cx) z.  The margin of one pixel is far beyond any rounding of either form, so this never
+	// drops a point the exact test keeps; false for NaN.  A wave whose 64 points all lie outside leaves here as a whole.
+	const double xk = x * v.kx, yk = y * v.ky;
+	if (xk < -(v.cx + 1.5) * z || xk > ((double)v.W + 0.5 - v.cx) * z || yk < -(v.cy + 1.5) * z || yk > ((double)v.H + 0.5 - v.cy) * z) return;
+	const double uf =floor((x / z) * v.kx + v.cx + 0.5), vf = floor((y / z) * v.ky + v.cy + 0.5);
+	if (!(uf >= 0.0 && uf < (double)v.W && vf >= 0.0 && vf < (double)v.H)) return;          // false for NaN
+	// 0 <= xi < W and 0 <= yi < H: pix lies inside the images
+	const size_t pix = (size_t)(int)vf * v.W + (int)uf;
+	const float Of = opacity[pix], Df = depth[pix];
+	if (!(Of >= v.min_opacity) || !(Df > 0.f)) return;
+	const float wf = weight ? weight[pix] : 1.f;
+	if (!(wf > 0.f)) return;
+	const double zd = v.inv_depth ? (double)Of / (double)Df : (double)Df / (double)Of;
+	if (!(zd <= v.max_depth)) return;
+	const double sdf = zd - z;
+	if (!(sdf >= -v.trunc)) return;
+	const double d = fmin(1.0, sdf / v.trunc), w = (double)wf;
+	const double W0 = (double)wsum[idx], Wn = W0 + w;          // > 0: w > 0 and the stored sum is never negative
+	tsdf[idx] = (float)(((double)tsdf[idx] * W0 + d * w) / Wn);
+	if (color) {
+		const size_t plane = (size_t)v.H * v.W;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			float* dst = color + (size_t)c * L.n + idx;
+			*dst = (float)(((double)*dst * W0 + (double)image[c * plane + pix] * w) / Wn);
+		}
+	}
+	wsum[idx] = (float)fmin(Wn, v.max_weight);
+}
+
+// ---- extraction ----
+
+// the tet-vertex corner bits (x = 1, y = 2, z = 4) of the 6 Kuhn tets, 4 bits each from tet vertex 0 up; tets 0, 3, 4 have an even axis order
+__device__ constexpr uint16_t TET_CORNERS[6] = { 0x7310, 0x7510, 0x7320, 0x7620, 0x7540, 0x7640 };
+// the slots +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z as corner bits, and the slot of a corner-bit difference d in nibble d
+__device__ constexpr uint8_t BITS_OF_SLOT[7] = { 1, 2, 4, 3, 5, 6, 7 };
+constexpr uint32_t SLOT_OF_BITS = 0x65423100u;
+// the inside sets (bit m: tet vertex m is inside) whose triangles are reversed: even axis orders, then odd (the complement among the mixed sets);
+// pinned by exact face equality against the geometric rule of tests/tsdf_ref.py
+constexpr uint32_t REV_EVEN = 0x25A4, REV_ODD = 0x5A5A;
+
+struct PointClass {
+	uint32_t in8;           // bit b: corner p + b exists and is inside
+	uint32_t vmask;         // the active slots of the 7 edges p owns
+	bool cell;              // p's own cell is valid and has corners of both signs
+};
+
+__device__ __forceinline__ void split_index(const Lattice& L, unsigned idx, int& i, int& j, int& k) {
+	const unsigned row = idx / (unsigned)L.nx;
+	i = (int)(idx - row * (unsigned)L.nx); k = (int)(row / (unsigned)L.ny); j = (int)(row - (unsigned)k * (unsigned)L.ny);
+}
+
+// idx < L.n.  Reads tsdf at p + {0, 1}^3 and, when those differ in sign, wsum at p + {-1, 0, 1}^3, inside the lattice only.
+__device__ __forceinline__ PointClass classify(const Lattice& L, const float* __restrict__ tsdf, const float* __restrict__ wsum, float min_weight,
+	unsigned idx, int i, int j, int k) {
+	PointClass pc; pc.in8 = 0; pc.vmask = 0; pc.cell = false;
+	const size_t sx = 1, sy = (size_t)L.nx, sz = (size_t)L.nx * L.ny;
+	uint32_t have = 0;
+#pragma unroll
+	for (int b = 0; b < 8; b++) {
+		const int dx = b & 1, dy = (b >> 1) & 1, dz = b >> 2;
+		if (i + dx < L.nx && j + dy < L.ny && k + dz < L.nz) {
+			have |= 1u << b;
+			if (tsdf[idx + dx * sx + dy * sy + dz * sz] < 0.f) pc.in8 |= 1u << b;
+		}
+	}
+	if (pc.in8 == 0 || pc.in8 == have) return pc;              // one sign: no edge of p and no tet of its cell is cut
+	uint32_t ok = 0;                                            // bit ((dz + 1) 3 + dy + 1) 3 + dx + 1: the corner exists and has wsum >= min_weight
+#pragma unroll
+	for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+		for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+			for (int dx = -1; dx <= 1; dx++) {
+				const int a = i + dx, b = j + dy, c = k + dz;
+				if (a >= 0 && a < L.nx && b >= 0 && b < L.ny && c >= 0 && c < L.nz && wsum[(size_t)c * sz + (size_t)b * sy + (size_t)a] >= min_weight)
+					ok |= 1u << (((dz + 1) * 3 + dy + 1) * 3 + dx + 1);
+			}
+	// cell with lowest corner p + (a, b, c), a, b, c in {-1, 0}: valid when its 8 corners are
+	uint32_t cells = 0;                                         // bit (c + 1) 4 + (b + 1) 2 + (a + 1)
+#pragma unroll
+	for (int q = 0; q < 8; q++) {
+		const int a = (q & 1) - 1, b = ((q >> 1) & 1) - 1, c = (q >> 2) - 1;
+		uint32_t need = 0;
+#pragma unroll
+		for (int e = 0; e < 8; e++) need |= 1u << (((c + (e >> 2) + 1) * 3 + b + ((e >> 1) & 1) + 1) * 3 + a + (e & 1) + 1);
+		if ((ok & need) == need) cells |= 1u << q;
+	}
+	const bool in_p = pc.in8 & 1u;
+#pragma unroll
+	for (int s = 0; s < 7; s++) {
+		const int ob = BITS_OF_SLOT[s];
+		if (!((have >> ob) & 1u) || (((pc.in8 >> ob) & 1u) != 0) == in_p) continue;
+		// the cells that contain the edge: along an axis the edge spans, the cell starts at p; along the others at p - 1 or p
+		uint32_t with = 0;
+#pragma unroll
+		for (int q = 0; q < 8; q++) if ((q & ob) == ob) with |= 1u << q;      // q's bit of an axis set: the cell starts at p on that axis
+		if (cells & with) pc.vmask |= 1u << s;
+	}
+	pc.cell = (cells >> 7) & 1u;                                // its corners are p + {0, 1}^3, of both signs here
+	return pc;
+}
+
+// faces of the valid mixed cell with corner signs in8
+__device__ __forceinline__ uint32_t cell_faces(uint32_t in8) {
+	uint32_t f = 0;
+#pragma unroll
+	for (int t = 0; t < 6; t++) {
+		const uint32_t c = TET_CORNERS[t];
+		const int n = (int)((in8 >> (c & 15)) & 1u) + (int)((in8 >> ((c >> 4) & 15)) & 1u) + (int)((in8 >> ((c >> 8) & 15)) & 1u) + (int)((in8 >> (c >> 12)) & 1u);
+		f += n == 2 ? 2u : (n == 1 || n == 3 ? 1u : 0u);
+	}
+	return f;
+}
+
+// exclusive prefix of v over the 256 threads of the workgroup, in thread order; total: the sum.  Every thread calls it.
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave /* [5] */, uint32_t& total) {
+	const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+	uint32_t incl = v;
+#pragma unroll
+	for (int off = 1; off < WAVE; off <<= 1) {
+		const uint32_t o = __shfl_up(incl, off, WAVE);
+		if (lane >= off) incl += o;
+	}
+	__syncthreads();                                            // a previous use of s_wave is over
+	if (lane == WAVE - 1) s_wave[wid] = incl;
+	__syncthreads();
+	uint32_t before = 0; total = 0;
+#pragma unroll
+	for (int w = 0; w < TSDF_THREADS / WAVE; w++) { const uint32_t t = s_wave[w]; if (w < wid) before += t; total += t; }
+	return before + incl - v;
+}
+
+// EMIT false: the three counts of the chunk.  EMIT true: the chunk's vertices and, when it has any, its owner words.
+template <bool EMIT>
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_points_kernel(Lattice L, const float* __restrict__ tsdf, const float* __restrict__ wsum,
+	const float* __restrict__ color, float min_weight, uint32_t* __restrict__ cv, uint32_t* __restrict__ cf, uint32_t* __restrict__ ce,
+	uint32_t* __restrict__ owners, unsigned n_owner_chunks, size_t n_vertices, float* __restrict__ vertices, float* __restrict__ colors) {
+	__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
+	const unsigned chunk = blockIdx.x, idx = chunk * (unsigned)TSDF_THREADS + threadIdx.x;
+	PointClass pc; pc.in8 = 0; pc.vmask = 0; pc.cell = false;
+	int i = 0, j = 0, k = 0;
+	if (idx < L.n) { split_index(L, idx, i, j, k); pc = classify(L, tsdf, wsum, min_weight, idx, i, j, k); }
+	uint32_t nv_chunk, nf_chunk;
+	const uint32_t local = block_exclusive((uint32_t)__popc(pc.vmask), s_wave, nv_chunk);
+	if (!EMIT) {
+		block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
+		if (threadIdx.x == 0) { cv[chunk] = nv_chunk; cf[chunk] = nf_chunk; ce[chunk] = nv_chunk ? 1u : 0u; }
+		return;
+	}
+	if (nv_chunk == 0) return;                                  // workgroup-uniform
+	// cv, ce: scanned.  ce[chunk] < n_owner_chunks for a chunk with vertices
+	owners[(size_t)min(ce[chunk], n_owner_chunks - 1u) * TSDF_THREADS + threadIdx.x] = (local << 8) | pc.vmask;
+	if (!pc.vmask) return;
+	const size_t sy = (size_t)L.nx, sz = (size_t)L.nx * L.ny;
+	const double Tp = (double)tsdf[idx];
+	size_t id = (size_t)cv[chunk] + local;
+#pragma unroll
+	for (int s = 0; s < 7; s++) {
+		if (!((pc.vmask >> s) & 1u) || id >= n_vertices) continue;      // id < n_vertices for the volume that was counted
+		const int ob = BITS_OF_SLOT[s], dx = ob & 1, dy = (ob >> 1) & 1, dz = ob >> 2;
+		const size_t q = idx + dx + dy * sy + dz * sz;          // inside the lattice: the slot is active
+		const double Tq = (double)tsdf[q], t = Tp / (Tp - Tq);  // the signs differ: Tp != Tq
+		vertices[3 * id + 0] = (float)(L.o[0] + L.vs * ((double)i + t * (double)dx));
+		vertices[3 * id + 1] = (float)(L.o[1] + L.vs * ((double)j + t * (double)dy));
+		vertices[3 * id + 2] = (float)(L.o[2] + L.vs * ((double)k + t * (double)dz));
+		if (colors) {
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				const double Cp = (double)color[(size_t)c * L.n + idx], Cq = (double)color[(size_t)c * L.n + q];
+				colors[3 * id + c] = (float)(Cp + t * (Cq - Cp));
+			}
+		}
+		id++;
+	}
+}
+
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(Lattice L, const float* __restrict__ tsdf, const float* __restrict__ wsum, float min_weight,
+	const uint32_t* __restrict__ cv, const uint32_t* __restrict__ cf, const uint32_t* __restrict__ ce, const uint32_t* __restrict__ owners,
+	unsigned n_owner_chunks, size_t n_faces, int* __restrict__ faces) {
+	__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
+	const unsigned chunk = blockIdx.x, idx = chunk * (unsigned)TSDF_THREADS + threadIdx.x;
+	PointClass pc; pc.in8 = 0; pc.vmask = 0; pc.cell = false;
+	if (idx < L.n) { int i, j, k; split_index(L, idx, i, j, k); pc = classify(L, tsdf, wsum, min_weight, idx, i, j, k); }
+	uint32_t nf_chunk;
+	const uint32_t local = block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
+	if (!pc.cell) return;
+	const unsigned sy = (unsigned)L.nx, sz = (unsigned)L.nx * (unsigned)L.ny;
+	// the vertex on the edge between corners lo < hi (corner bits, lo a subset of hi) of this cell: it exists, so its owner's chunk has an owner word
+	auto vid = [&](int lo, int hi) -> int {
+		const unsigned owner = idx + (lo & 1) + ((lo >> 1) & 1) * sy + (lo >> 2) * sz;      // a corner of a valid cell: inside the lattice
+		const unsigned oc = owner / (unsigned)TSDF_THREADS, ol = owner % (unsigned)TSDF_THREADS;
+		const uint32_t word = owners[(size_t)min(ce[oc], n_owner_chunks - 1u) * TSDF_THREADS + ol];
+		return (int)(cv[oc] + (word >> 8) + (uint32_t)__popc(word & ((1u << ((SLOT_OF_BITS >> (4 * (hi ^ lo))) & 15u)) - 1u)));
+	};
+	size_t f = (size_t)cf[chunk] + local;
+#pragma unroll
+	for (int t = 0; t < 6; t++) {
+		const uint32_t c = TET_CORNERS[t];
+		uint32_t m = 0;                                         // bit q: tet vertex q is inside
+#pragma unroll
+		for (int q = 0; q < 4; q++) m |= ((pc.in8 >> ((c >> (4 * q)) & 15u)) & 1u) << q;
+		const int n = __popc(m);
+		if (n == 0 || n == 4) continue;
+		// the vertex on the edge between tet vertices a and b
+		auto e = [&](int a, int b) -> int { return vid((int)((c >> (4 * min(a, b))) & 15u), (int)((c >> (4 * max(a, b))) & 15u)); };
+		const bool rev = ((t == 0 || t == 3 || t == 4 ? REV_EVEN : REV_ODD) >> m) & 1u;
+		auto put = [&](int p0, int p1, int p2) {
+			if (f < n_faces) { faces[3 * f + 0] = rev ? p2 : p0; faces[3 * f + 1] = p1; faces[3 * f + 2] = rev ? p0 : p2; }
+			f++;
+		};
+		if (n == 2) {
+			const uint32_t out = ~m & 15u;
+			const int a = __ffs((int)m) - 1, b = 31 - __clz((int)m), o0 = __ffs((int)out) - 1, o1 = 31 - __clz((int)out);
+			const int q0 = e(a, o0), q1 = e(a, o1), q2 = e(b, o1), q3 = e(b, o0);
+			put(q0, q1, q2);
+			put(q0, q2, q3);
+		} else {
+			const uint32_t lone = n == 1 ? m : (~m & 15u);
+			const int a = __ffs((int)lone) - 1;
+			uint32_t rest = ~lone & 15u;
+			const int r0 = __ffs((int)rest) - 1; rest &= rest - 1u;
+			const int r1 = __ffs((int)rest) - 1; rest &= rest - 1u;
+			const int r2 = __ffs((int)rest) - 1;
+			if (n == 1) put(e(a, r0), e(a, r1), e(a, r2));
+			else put(e(a, r2), e(a, r1), e(a, r0));
+		}
+	}
+}
+
+bool tsdf_positive(float x) { return std::isfinite(x) && x > 0.f; }
+
+// 0: `L` is set; 1: an empty lattice; -1: refused
+int check_volume(const std::string& name, const adgs_tsdf_volume* vol, Lattice& L) {
+	if (vol->struct_bytes < (int)sizeof(adgs_tsdf_volume)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_volume"); return -1; }
+	if (vol->nx < 0 || vol->ny < 0 || vol->nz < 0) { set_error(name + ": negative nx, ny or nz"); return -1; }
+	const unsigned long long xy = (unsigned long long)vol->nx * (unsigned long long)vol->ny;
+	if (xy > (unsigned long long)INT_MAX || xy * (unsigned long long)vol->nz > (unsigned long long)INT_MAX) {
+		set_error(name + ": nx * ny * nz must be below 2^31"); return -1;
+	}
+	if (!tsdf_positive(vol->voxel_size)) { set_error(name + ": voxel_size must be finite and > 0"); return -1; }
+	for (int a = 0; a < 3; a++)
+		if (!std::isfinite(vol->origin[a])) { set_error(name + ": the origin must be finite"); return -1; }
+	L.nx = vol->nx; L.ny = vol->ny; L.nz = vol->nz;
+	L.n = (unsigned)(xy * (unsigned long long)vol->nz);
+	L.vs = (double)vol->voxel_size;
+	for (int a = 0; a < 3; a++) L.o[a] = (double)vol->origin[a];
+	return L.n == 0 ? 1 : 0;
+}
+
+unsigned chunks_of(const Lattice& L) { return (L.n + (unsigned)TSDF_THREADS - 1u) / (unsigned)TSDF_THREADS; }
+
+// the scratch of the extraction: three uint32 per chunk (vertices, faces, has-vertices; scanned in place), the 64-bit totals, the scan's own scratch
+struct ExtractTemp { uint32_t *cv, *cf, *ce; unsigned long long* totals; char* scan; size_t bytes; };
+ExtractTemp carve_temp(char* base, size_t chunks) {
+	Carver c(base);
+	ExtractTemp t;
+	t.cv = c.take<uint32_t>(chunks); t.cf = c.take<uint32_t>(chunks); t.ce = c.take<uint32_t>(chunks);
+	t.totals = c.take<unsigned long long>(3 * SCAN_AUX_SLOTS);
+	t.scan = c.take<char>(scan_temp_bytes(chunks));
+	t.bytes = c.size();
+	return t;
+}
+
+} // namespace
+} // namespace adgs
+
+using namespace adgs;
+
+extern "C" int adgs_tsdf_integrate(const adgs_tsdf_volume* vol, const adgs_tsdf_view* view, const float* depth, const float* opacity, const float* image,
+	const float* weight, float* tsdf, float* wsum, float* color, void* stream_) {
+	const std::string name("adgs_tsdf_integrate");
+	if (!vol || !view || !depth || !opacity || !tsdf || !wsum) { set_error(name + ": NULL pointer"); return -1; }
+	Lattice L;
+	const int c = check_volume(name, vol, L);
+	if (c < 0) return -1;
+	if (view->struct_bytes < (int)sizeof(adgs_tsdf_view)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_view"); return -1; }
+	if (view->H < 0 || view->W < 0) { set_error(name + ": negative H or W"); return -1; }
+	if ((long long)view->H * view->W > (long long)INT_MAX) { set_error(name + ": H * W exceeds INT_MAX"); return -1; }
+	if (!tsdf_positive(view->tanfovx) || !tsdf_positive(view->tanfovy)) { set_error(name + ": tanfovx and tanfovy must be finite and > 0"); return -1; }
+	if (!tsdf_positive(view->trunc)) { set_error(name + ": trunc must be finite and > 0"); return -1; }
+	if (!(tsdf_positive(view->min_opacity) && view->min_opacity <= 1.f)) { set_error(name + ": min_opacity must lie in (0, 1]"); return -1; }
+	if (!(view->max_weight > 0.f)) { set_error(name + ": max_weight must be > 0"); return -1; }
+	if (!(std::isfinite(view->near) && view->near >= 0.f)) { set_error(name + ": near must be finite and >= 0"); return -1; }
+	for (int i = 0; i < 12; i++)
+		if (!std::isfinite(view->pose[i])) { set_error(name + ": the pose must be finite"); return -1; }
+	if ((image != nullptr) != (color != nullptr)) { set_error(name + ": image and color must be given together"); return -1; }
+	if (c == 1 || view->H == 0 || view->W == 0) return 0;
+	TsdfView v;
+	v.H = view->H; v.W = view->W; v.inv_depth = view->inv_depth ? 1 : 0;
+	v.kx = (double)view->W / (2.0 * (double)view->tanfovx); v.ky = (double)view->H / (2.0 * (double)view->tanfovy);
+	v.cx = 0.5 * (double)(view->W - 1); v.cy = 0.5 * (double)(view->H - 1);
+	for (int i = 0; i < 9; i++) v.R[i] = view->pose[i];
+	for (int i = 0; i < 3; i++) v.t[i] = view->pose[9 + i];
+	v.near = (double)view->near; v.max_depth = (double)view->max_depth; v.trunc = (double)view->trunc; v.max_weight = (double)view->max_weight;
+	v.min_opacity = view->min_opacity;
+	hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(chunks_of(L)), dim3(TSDF_THREADS), 0, (hipStream_t)stream_, L, v, depth, opacity, image, weight, tsdf,
+		wsum, color);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+
+extern "C" size_t adgs_tsdf_extract_temp_bytes(const adgs_tsdf_volume* vol) {
+	Lattice L;
+	if (!vol || check_volume("adgs_tsdf_extract_temp_bytes", vol, L) < 0) return 0;
+	return carve_temp(nullptr, chunks_of(L)).bytes;
+}
+
+extern "C" size_t adgs_tsdf_extract_owner_bytes(long long nonempty_chunks) {
+	return nonempty_chunks > 0 ? (size_t)nonempty_chunks * ADGS_TSDF_OWNER_BYTES_PER_CHUNK : 0;
+}
+
+extern "C" int adgs_tsdf_extract_count(const adgs_tsdf_volume* vol, const float* tsdf, const float* wsum, float min_weight, void* temp, long long* counts,
+	void* stream_) {
+	const std::string name("adgs_tsdf_extract_count");
+	if (!vol || !tsdf || !wsum || !temp || !counts) { set_error(name + ": NULL pointer"); return -1; }
+	Lattice L;
+	const int c = check_volume(name, vol, L);
+	if (c < 0) return -1;
+	counts[0] = counts[1] = counts[2] = 0;
+	if (c == 1 || L.nx < 2 || L.ny < 2 || L.nz < 2) return 0;     // no cell, hence no vertex and no face
+	hipStream_t stream = (hipStream_t)stream_;
+	const unsigned chunks = chunks_of(L);
+	const ExtractTemp t = carve_temp((char*)temp, chunks);
+	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 3 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
+	hipLaunchKernelGGL(tsdf_points_kernel<false>, dim3(chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, (const float*)nullptr, min_weight, t.cv, t.cf,
+		t.ce, (uint32_t*)nullptr, 0u, (size_t)0, (float*)nullptr, (float*)nullptr);
+	ADGS_HIP_CHECK(hipGetLastError());
+	uint32_t* rows[3] = { t.cv, t.cf, t.ce };
+	for (int r = 0; r < 3; r++)
+		if (exclusive_scan_u32_sum(rows[r], rows[r], chunks, t.scan, rows[r], t.totals + r * SCAN_AUX_SLOTS, stream) != 0) return -1;
+	unsigned long long host[3 * SCAN_AUX_SLOTS];
+	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
+	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
+	unsigned long long sum[3] = { 0, 0, 0 };
+	for (int r = 0; r < 3; r++)
+		for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
+	if (sum[0] > (unsigned long long)INT_MAX || sum[1] > (unsigned long long)INT_MAX) {
+		set_error(name + ": the mesh has " + std::to_string(sum[0]) + " vertices and " + std::to_string(sum[1]) + " faces; more than INT_MAX of either is refused");
+		return -1;
+	}
+	for (int r = 0; r < 3; r++) counts[r] = (long long)sum[r];
+	return 0;
+}
+
+extern "C" int adgs_tsdf_extract_emit(const adgs_tsdf_volume* vol, const float* tsdf, const float* wsum, const float* color, float min_weight,
+	const void* temp, void* owners, const long long* counts, float* vertices, int* faces, float* colors, void* stream_) {
+	const std::string name("adgs_tsdf_extract_emit");
+	if (!vol || !tsdf || !wsum || !temp || !counts) { set_error(name + ": NULL pointer"); return -1; }
+	Lattice L;
+	const int c = check_volume(name, vol, L);
+	if (c < 0) return -1;
+	const long long V = counts[0], F = counts[1], E = counts[2];
+	const long long chunks = c == 1 ? 0 : (long long)chunks_of(L);
+	if (V < 0 || F < 0 || E < 0 || V > (long long)INT_MAX || F > (long long)INT_MAX || E > chunks || E > V) {
+		set_error(name + ": counts are not what adgs_tsdf_extract_count returned for this volume"); return -1;
+	}
+	if ((V > 0 && !vertices) || (F > 0 && !faces) || (E > 0 && !owners)) { set_error(name + ": NULL vertices, faces or owners"); return -1; }
+	if ((color != nullptr) != (colors != nullptr)) { set_error(name + ": color and colors must be given together"); return -1; }
+	if (V == 0 || E == 0) return 0;                              // no vertex, hence no face
+	hipStream_t stream = (hipStream_t)stream_;
+	const ExtractTemp t = carve_temp((char*)temp, (size_t)chunks);
+	hipLaunchKernelGGL(tsdf_points_kernel<true>, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, color, min_weight, t.cv, t.cf, t.ce,
+		(uint32_t*)owners, (unsigned)E, (size_t)V, vertices, colors);
+	ADGS_HIP_CHECK(hipGetLastError());
+	if (F > 0) {
+		hipLaunchKernelGGL(tsdf_faces_kernel, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, min_weight, (const uint32_t*)t.cv,
+			(const uint32_t*)t.cf, (const uint32_t*)t.ce, (const uint32_t*)owners, (unsigned)E, (size_t)F, faces);
+		ADGS_HIP_CHECK(hipGetLastError());
+	}
+	return 0;
+}
