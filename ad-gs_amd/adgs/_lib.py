@@ -162,6 +162,15 @@ SIGNATURES = {
     "adgs_tsdf_extract_owner_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "adgs_tsdf_extract_count": (c_i, [c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
     "adgs_tsdf_extract_emit": (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_mesh.h
+    "adgs_mesh_label_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_mesh_label": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_mesh_table": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_mesh_keep_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_mesh_keep_count": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_mesh_keep_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_mesh_normals_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_mesh_vertex_normals": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

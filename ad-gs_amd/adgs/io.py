@@ -75,11 +75,11 @@ def read_ply(path):
     return [n for n, _ in props], cols
 
 
-def write_mesh_ply(path, vertices, faces, colors=None):
-    """A triangle mesh as a binary little-endian PLY: `vertex` (float x, y, z and, with colours, uchar red, green, blue) and `face`
-    (list uchar int vertex_indices), the layout MeshLab, Blender and Open3D read.  vertices [V, 3], faces [F, 3], colors [V, 3] in
-    [0, 1] or None: tensors (any device) or arrays.  A colour becomes (255 * clip(c, 0, 1)) truncated to uint8, as the evaluation's
-    to8b does."""
+def write_mesh_ply(path, vertices, faces, colors=None, normals=None):
+    """A triangle mesh as a binary little-endian PLY: `vertex` (float x, y, z, with normals float nx, ny, nz and, with colours, uchar red,
+    green, blue) and `face` (list uchar int vertex_indices), the layout MeshLab, Blender and Open3D read.  vertices [V, 3], faces [F, 3],
+    colors [V, 3] in [0, 1] or None, normals [V, 3] (adgs.mesh.vertex_normals) or None: tensors (any device) or arrays.  A colour becomes
+    (255 * clip(c, 0, 1)) truncated to uint8, as the evaluation's to8b does.  Without normals the file is what it was before they existed."""
     host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v, f = np.ascontiguousarray(host(vertices), dtype='<f4'), host(faces)
     if v.ndim != 2 or v.shape[1] != 3:
@@ -90,6 +90,12 @@ def write_mesh_ply(path, vertices, faces, colors=None):
         raise ValueError("write_mesh_ply: faces must index the %d vertices" % v.shape[0])
     props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % v.shape[0]
+    if normals is not None:
+        nrm = np.ascontiguousarray(host(normals), dtype='<f4')
+        if nrm.shape != v.shape:
+            raise ValueError("write_mesh_ply: normals must be [V, 3] = %s, got %s" % (v.shape, nrm.shape))
+        props += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         c = host(colors)
         if c.shape != v.shape:
@@ -100,6 +106,9 @@ def write_mesh_ply(path, vertices, faces, colors=None):
     vrec = np.empty(v.shape[0], dtype=np.dtype(props))
     for a, n in enumerate("xyz"):
         vrec[n] = v[:, a]
+    if normals is not None:
+        for a, n in enumerate(("nx", "ny", "nz")):
+            vrec[n] = nrm[:, a]
     if colors is not None:
         c8 = (255 * np.clip(c.astype(np.float32), 0, 1)).astype(np.uint8)
         for a, n in enumerate(("red", "green", "blue")):
@@ -114,9 +123,10 @@ def write_mesh_ply(path, vertices, faces, colors=None):
         fh.write(frec.tobytes())
 
 
-def read_mesh_ply(path):
+def read_mesh_ply(path, normals=False):
     """A binary little-endian triangle-mesh PLY as write_mesh_ply writes it -> (vertices [V, 3] float32, faces [F, 3] int32,
-    colors [V, 3] uint8 or None), numpy arrays.  Extra scalar vertex properties are skipped; a face that is not a triangle is refused."""
+    colors [V, 3] uint8 or None), numpy arrays; with normals=True a 4-tuple whose last element is the [V, 3] float32 nx, ny, nz or None.
+    Other scalar vertex properties are skipped; a face that is not a triangle is refused."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError("%s is not a PLY file" % path)
@@ -138,7 +148,7 @@ def read_mesh_ply(path):
                 break
         if fmt != "binary_little_endian":
             raise ValueError("%s: read_mesh_ply reads binary_little_endian files, this one is %s" % (path, fmt))
-        vertices = colors = None
+        vertices = colors = vnormals = None
         faces = np.zeros((0, 3), np.int32)
         for name, count, props in elements:
             if name == "face":
@@ -158,9 +168,11 @@ def read_mesh_ply(path):
                     vertices = np.stack([data[n] for n in "xyz"], axis=1).astype(np.float32) if count else np.zeros((0, 3), np.float32)
                     if all(n in rec.names for n in ("red", "green", "blue")):
                         colors = np.stack([data[n] for n in ("red", "green", "blue")], axis=1).astype(np.uint8) if count else np.zeros((0, 3), np.uint8)
+                    if all(n in rec.names for n in ("nx", "ny", "nz")):
+                        vnormals = np.stack([data[n] for n in ("nx", "ny", "nz")], axis=1).astype(np.float32) if count else np.zeros((0, 3), np.float32)
     if vertices is None:
         raise ValueError("%s has no vertex element" % path)
-    return vertices, faces, colors
+    return (vertices, faces, colors, vnormals) if normals else (vertices, faces, colors)
 
 
 def save_ply(model, path):

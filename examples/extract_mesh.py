@@ -4,9 +4,13 @@ volume over the static Gaussians' box, extract the surface by marching tetrahedr
 
     for camera:  render(camera)                         one time stamp per render
                  -> vol.integrate(depth, img_opacity, (camera, pose), image=render, weight=static)
-    vol.extract_mesh() -> adgs.io.write_mesh_ply
+    vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.mesh.vertex_normals] -> adgs.io.write_mesh_ply
 
     python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json]
+                                    [--keep-largest K] [--min-faces m] [--normals]
+
+--keep-largest / --min-faces (off by default; either one turns the clean-up on, the other then takes its 2DGS default of 50) drop the small
+connected components of the mesh, --normals writes area-weighted vertex normals into the PLY (adgs.mesh).
 
 Synthetic scene: a cloud of random Gaussians is no surface, so the mesh is a crust around what the cameras saw of it --
 the point here is the loop and its cost.  The cameras advance 0.35 m per view along the viewing direction with a small alternating yaw
@@ -28,9 +32,9 @@ for p in (ROOT, os.path.join(ROOT, "ad-gs_amd"), os.path.join(ROOT, "examples"))
 from multiview_step import neighbour_of  # noqa: E402
 
 
-def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None):
+def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False):
     import torch
-    from adgs import io, synthetic, tsdf
+    from adgs import io, mesh, synthetic, tsdf
     from adgs.model import SyntheticGaussianModel
     from gaussian_renderer import render
     device = device or torch.device("cuda", 0)
@@ -59,10 +63,22 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None):
     vertices, faces, colors = vol.extract_mesh(min_weight=1.0)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    io.write_mesh_ply(out, vertices, faces, colors)
-    v2, f2, c2 = io.read_mesh_ply(out)
+    extracted = {"vertices": int(vertices.shape[0]), "faces": int(faces.shape[0])}
+    cleanup = None
+    if keep_largest is not None or min_faces is not None:
+        K, m = 50 if keep_largest is None else keep_largest, 50 if min_faces is None else min_faces
+        comps = mesh.connected_components(faces, vertices.shape[0])
+        keep = comps.select(largest=K, min_faces=m)
+        vertices, faces, colors, _ = mesh.keep_components(comps, keep, vertices, faces, colors=colors)
+        cleanup = {"largest": K, "min_faces": m, "components": len(comps), "kept_components": int(keep.sum())}
+    vnormals = mesh.vertex_normals(vertices, faces) if normals else None
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    io.write_mesh_ply(out, vertices, faces, colors, normals=vnormals)
+    v2, f2, c2, n2 = io.read_mesh_ply(out, normals=True)
     assert v2.shape == tuple(vertices.shape) and f2.shape == tuple(faces.shape) and c2.shape == tuple(colors.shape)
-    return {"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras, "dims": list(vol.dims),
+    assert (n2 is None) == (vnormals is None) and (n2 is None or n2.shape == v2.shape)
+    return {"extracted": extracted, "cleanup": cleanup, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras, "dims": list(vol.dims),
             "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()), "vertices": int(vertices.shape[0]),
             "faces": int(faces.shape[0]), "render_and_integrate_ms": 1e3 * (t1 - t0), "extract_ms": 1e3 * (t2 - t1), "ply": out,
             "ply_bytes": os.path.getsize(out)}
@@ -75,11 +91,14 @@ def main():
     ap.add_argument("--resolution", type=int, default=160, help="voxels along the longest side of the static Gaussians' box")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep the components with at least as many faces as the K-th largest")
+    ap.add_argument("--min-faces", type=int, default=None, metavar="m", help="and with at least m faces")
+    ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
-    res = run(a.config, a.cameras, a.resolution, a.out)
+    res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals)
     if a.json:
         print(json.dumps(res))
     else:
@@ -88,6 +107,12 @@ def main():
                   res["config"], res["gaussians"], res["cameras"], res["image"][0], res["image"][1], *res["dims"], res["voxel_size"],
                   100 * res["observed_share"], res["vertices"], res["faces"], res["render_and_integrate_ms"], res["extract_ms"], res["ply"],
                   res["ply_bytes"]))
+        if res["cleanup"] or res["normals"]:
+            c = res["cleanup"]
+            print("extracted V %d, F %d%s -> V %d, F %d%s; clean-up and normals %.1f ms" % (
+                res["extracted"]["vertices"], res["extracted"]["faces"],
+                "; %d components, kept %d (largest %d, min_faces %d)" % (c["components"], c["kept_components"], c["largest"], c["min_faces"]) if c else "",
+                res["vertices"], res["faces"], ", with vertex normals" if res["normals"] else "", res["cleanup_and_normals_ms"]))
 
 
 if __name__ == "__main__":
