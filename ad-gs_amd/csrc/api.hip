@@ -110,7 +110,7 @@ struct GeomStateV2 {
 	float* ddir;      // [9][P]: d colour / d view direction of the raw-SH path (PreprocessArgs.ddir)
 	// bucket binning (binning.hip): ONE block of counters the frame's prologue zeroes -- pair counts per cell, the fine-tile total slots,
 	// the device-side (pairs, overflow, ...) words -- then the cell starts, the frame's snapshot of the slab bounds and the counts matrix
-	uint32_t* counters; uint32_t* cell_start; uint2* cell_work; uint32_t* bounds; uint32_t* counts;      // counts[ceil(P / 256)][ncells]: pairs per (preprocess workgroup, cell); bounds[ncells][SLAB_ROW]; cell_work[ncells + 1]
+	uint32_t* counters; uint32_t* cell_start; uint2* cell_work; uint32_t* bounds; uint32_t* counts;      // counts[ncells][count_row_stride(ceil(P / 256))]: pairs per (cell, preprocess workgroup), cell-major; bounds[ncells][SLAB_ROW]; cell_work[ncells + 1]
 	static constexpr size_t COUNTER_WORDS = MAX_CELLS + 2 * SCAN_AUX_SLOTS + 8;
 	uint32_t* cell_count() const { return counters; }
 	unsigned long long* bucket_fine_total() const { return reinterpret_cast<unsigned long long*>(counters + MAX_CELLS); }
@@ -135,7 +135,7 @@ struct GeomStateV2 {
 		g.ddir = with_ddir ? c.take<float>(P * 9) : nullptr;
 		const size_t nc = std::min<size_t>(ncells, (size_t)MAX_CELLS + 1);      // last: the backward carves without them
 		g.bounds = c.take<uint32_t>(nc * SLAB_ROW);
-		g.counts = c.take<uint32_t>(((P + 255) / 256) * nc);
+		g.counts = c.take<uint32_t>(count_row_stride((int)((P + 255) / 256)) * nc);
 		if (bytes) *bytes = c.size();
 		return g;
 	}
@@ -576,7 +576,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 		}
 		const bool sort_fallback_fits = v2_keys_fit(gx, gy, cell_tiles);      // may this frame still fall back to the sort (chunk table full)?
 		size_t gb = 0, ib = 0;
-		const size_t count_cells = buckets ? ncells : 0;      // the counts matrix [ceil(P / 256)][ncells] and the snapshot of the slab bounds exist for bucket binning only
+		const size_t count_cells = buckets ? ncells : 0;      // the counts matrix [ncells][ceil(P / 256), padded to 4] and the snapshot of the slab bounds exist for bucket binning only
 		const bool with_ddir = training && sh_src && M == 16;
 		GeomStateV2::carve(nullptr, P, &gb, with_ddir, count_cells);
 		char* gch = geometryBuffer(geometryUser, gb);

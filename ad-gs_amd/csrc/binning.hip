@@ -5,16 +5,21 @@
 // 15-launch LSD radix sort of (cell | depth) keys and tile_ranges = 20 launches and ~175 us per C3 frame for 1.5 M pairs).
 // The lists of different coarse cells are independent sorting problems; nothing has to be sorted device-wide:
 //
-//   preprocess_fwd   counts the (cell, Gaussian) pairs of its 256 Gaussians per coarse cell in LDS and writes the row
-//                    counts[workgroup][cell] (no global atomics: scene Gaussians come in no spatial order, a workgroup touches every
-//                    cell, and atomics on a few hot lines serialise -- measured in rounds 2 and 6);
-//   cell_colscan     one workgroup per cell: exclusive prefix of the cell's column over the workgroups, in place + the cell total;
+//   preprocess_fwd   counts the (cell, Gaussian) pairs of its 256 Gaussians per coarse cell in LDS and writes them as its column of the
+//                    CELL-MAJOR matrix counts[cell][workgroup] (rows padded to 16 bytes: count_row_stride; no global atomics: scene
+//                    Gaussians come in no spatial order, a workgroup touches every cell, and atomics on a few hot lines serialise --
+//                    measured in rounds 2 and 6);
+//   cell_colscan     one workgroup per cell: exclusive prefix of the cell's row over the workgroups, in place + the cell total.  The row is
+//                    contiguous: 16-byte loads, 4096 workgroups per trip (the workgroup-major matrix of round 6 cost a 64-byte line per
+//                    word: 11.6 us at C3, now 5.1);
 //   cell_scan        ONE workgroup: exclusive scan of the cell totals -> cell ranges; the frame's totals and capacity check;
-//   cell_scatter     every pair goes to cell_start + counts[workgroup][cell] + (LDS atomic inside the workgroup): its depth key into one
+//                    (folded into cell_colscan's last workgroup behind an agent-scope ticket it was measured no faster: EXPERIMENTS.md)
+//   cell_scatter     every pair goes to cell_start + counts[cell][workgroup] + (LDS atomic inside the workgroup): its depth key into one
 //                    array, (Gaussian id, rectangle mask) into another -- any order inside a cell;
 //   slab_sort        a cell's list is only ever read front to back, so it is built as the concatenation of 2^lg independently sorted
 //                    DEPTH SLABS: workgroup (cell, slab) streams the cell's depth keys (4 bytes per entry, L2-resident), keeps the
-//                    entries of its slab -- the slab of a depth is a search over the cell's row of 127 bounds; ANY row
+//                    entries of its slab (compares, one popcount per thread, one prefix sum and one LDS atomic per wave and batch of
+//                    32 keys per thread; they land in LDS in any order) -- the slab of a depth is a search over the cell's row of 127 bounds; ANY row
 //                    contents give a monotone function of the depth, so correctness never depends on the bounds, only the balance
 //                    does --, counts the entries of the slabs below it (= where its output starts: no scan over slabs, no second
 //                    scatter), sorts its <= 4096 entries on (32 depth bits, Gaussian index) inside the CU (a histogram-equalised
@@ -46,6 +51,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
 	return v;
 }
 
+// The same prefix sum on the data-parallel-primitive path of the vector unit: shifts by 1, 2, 4, 8 inside every row of 16 lanes, then lane 15's
+// sum broadcast into rows 1 and 3 and lane 31's into rows 2 and 3 (a lane without a source adds the 0 of `old`).  Six vector adds and no
+// address registers -- slab_sort's key stream has none to spare: the __shfl_up form keeps six permute addresses live across its batch loop.
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp_u32(uint32_t v) {
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);      // row_shr:1
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);      // row_shr:2
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);      // row_shr:4
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);      // row_shr:8
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);      // row_bcast:15 -> rows 1, 3
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);      // row_bcast:31 -> rows 2, 3
+	return v;
+}
+
 // block-wide exclusive scan of one value per thread (1024 threads); returns the exclusive prefix, *total = sum over the block
 __device__ __forceinline__ uint32_t block_excl_scan_1024(uint32_t v, uint32_t* s_wave /* [16] */, uint32_t* total) {
 	const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
@@ -62,33 +80,42 @@ __device__ __forceinline__ uint32_t block_excl_scan_1024(uint32_t v, uint32_t* s
 
 __global__ void __launch_bounds__(256) bin_prepare_kernel(FramePrologue p) { run_frame_prologue(p); }
 
-// counts[nblocks][ncells] -> exclusive prefix over the workgroups of every cell's column (in place), column total -> cell_count
-__global__ void __launch_bounds__(256) cell_colscan_kernel(uint32_t* __restrict__ counts, int nblocks, int ncells, uint32_t* __restrict__ cell_count) {
-	__shared__ uint32_t s_w[256 / WAVE];
-	__shared__ uint32_t s_carry;
+// counts[ncells][count_row_stride(nblocks)] -> exclusive prefix over the workgroups of every cell's row (in place), row total -> cell_count.
+// One workgroup per cell; a thread owns CQ consecutive 16-byte words of the row (one 64-byte line, all four loads in flight): 4096 workgroups
+// of the preprocess per trip, so C3's 3907 are ONE trip over contiguous lines (the workgroup-major matrix cost a 64-byte line per word and
+// two trips); larger P loops.
+constexpr int CQ = 4;
+__global__ void __launch_bounds__(256) cell_colscan_kernel(uint32_t* __restrict__ counts, int nblocks, uint32_t* __restrict__ cell_count) {
+	__shared__ uint32_t s_w[2][256 / WAVE];      // double-buffered over the trips: one barrier per trip
 	const int c = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
-	if (tid == 0) s_carry = 0u;
-	__syncthreads();
-	for (int b0 = 0; b0 < nblocks; b0 += 256 * 8) {
-		uint32_t v[8], sum = 0;
+	const int nq = (int)(count_row_stride(nblocks) / 4);      // 16-byte words of a row (the last one may hold up to 3 pad words nobody wrote)
+	uint4* __restrict__ row = reinterpret_cast<uint4*>(counts + (size_t)c * count_row_stride(nblocks));
+	uint32_t carry = 0;      // block-uniform
+	for (int q0 = 0, trip = 0; q0 < nq; q0 += 256 * CQ, trip ^= 1) {
+		const int q = q0 + CQ * tid;
+		uint4 v[CQ];
 #pragma unroll
-		for (int k = 0; k < 8; k++) v[k] = counts[(size_t)min(b0 + tid * 8 + k, nblocks - 1) * ncells + c];      // unconditional, clamped: all eight in flight
+		for (int k = 0; k < CQ; k++) v[k] = row[min(q + k, nq - 1)];      // unconditional, clamped
+		uint32_t w[4 * CQ], sum = 0;
 #pragma unroll
-		for (int k = 0; k < 8; k++) { if (b0 + tid * 8 + k >= nblocks) v[k] = 0u; sum += v[k]; }
+		for (int k = 0; k < CQ; k++) { w[4 * k] = v[k].x; w[4 * k + 1] = v[k].y; w[4 * k + 2] = v[k].z; w[4 * k + 3] = v[k].w; }
+#pragma unroll
+		for (int k = 0; k < 4 * CQ; k++) { if (4 * q + k >= nblocks) w[k] = 0u; sum += w[k]; }      // beyond the row (clamped loads) and its pad words
 		const uint32_t incl = wave_incl_scan_u32(sum, lane);
-		if (lane == WAVE - 1) s_w[wid] = incl;
+		if (lane == WAVE - 1) s_w[trip][wid] = incl;
 		__syncthreads();
-		uint32_t off = s_carry, tot = 0;
+		uint32_t off = carry;
 #pragma unroll
-		for (int w = 0; w < 256 / WAVE; w++) { const uint32_t x = s_w[w]; if (w < wid) off += x; tot += x; }
+		for (int i = 0; i < 256 / WAVE; i++) { const uint32_t x = s_w[trip][i]; if (i < wid) off += x; carry += x; }
 		uint32_t run = off + incl - sum;
 #pragma unroll
-		for (int k = 0; k < 8; k++) { const int b = b0 + tid * 8 + k; if (b < nblocks) counts[(size_t)b * ncells + c] = run; run += v[k]; }
-		__syncthreads();
-		if (tid == 0) s_carry += tot;
-		__syncthreads();
+		for (int k = 0; k < CQ; k++) {
+			uint4 o;
+			o.x = run; run += w[4 * k]; o.y = run; run += w[4 * k + 1]; o.z = run; run += w[4 * k + 2]; o.w = run; run += w[4 * k + 3];
+			if (q + k < nq) row[q + k] = o;      // (pad words get a prefix too: inside the row, never read)
+		}
 	}
-	if (tid == 0) cell_count[c] = s_carry;
+	if (tid == 0) cell_count[c] = carry;
 }
 
 __global__ void __launch_bounds__(CS_THREADS) cell_scan_kernel(CellScanArgs a) {
@@ -139,7 +166,9 @@ __global__ void __launch_bounds__(256) cell_scatter_kernel(int P, const uint4* _
 	if (idx == 0) { *pool_cursor = 0u; slow_list[0] = 0u; }      // bookkeeping resets for the kernels that follow on this stream (the blend forward; slab_sort)
 	// this workgroup's slice of every cell's range: cell start + pairs of the workgroups before it (cell_colscan)
 	const uint4 d = dupinfo[min(idx, P - 1)];      // (rect min, rect max, depth bits, -): one coalesced 16-byte load, requested before the prologue's loads and its barrier
-	for (int c = threadIdx.x; c < ncells; c += 256) { s_cnt[c] = 0u; s_base[c] = cell_start[c] + counts[(size_t)blockIdx.x * ncells + c]; }
+	// (cell-major counts: one word of each of ncells lines, which this workgroup shares with its 15 neighbours in L2)
+	const size_t stride = count_row_stride((int)gridDim.x);
+	for (int c = threadIdx.x; c < ncells; c += 256) { s_cnt[c] = 0u; s_base[c] = cell_start[c] + counts[(size_t)c * stride + blockIdx.x]; }
 	__syncthreads();
 	if (idx >= P) return;
 	const uint32_t minx = d.x & 0xFFFFu, miny = d.x >> 16, maxx = d.y & 0xFFFFu, maxy = d.y >> 16;
@@ -494,14 +523,16 @@ __global__ void __launch_bounds__(GS_THREADS, 6) slab_sort_kernel(SlabSortArgs a
 		const uint32_t off = range.x & 3u, n_el = off + n_c;
 		const uint4* __restrict__ kw = reinterpret_cast<const uint4*>(a.rec_key + (range.x - off));
 		const uint32_t n_w = (n_el + 3u) >> 2;
-		const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
 		constexpr int SW = 8;
 		for (uint32_t wbase = 0; wbase < n_w; wbase += GS_THREADS * SW) {
 			uint4 kq[SW];
 #pragma unroll
 			for (int u = 0; u < SW; u++) kq[u] = kw[min(wbase + u * GS_THREADS + tid, n_w - 1u)];      // unconditional, clamped (the last word may reach 12 bytes past the cell: inside the buffer, rec_key is followed by the hand-over list)
-			// the wave's selected entries of this batch: ONE LDS atomic per wave and batch (one per 64 keys serialised the eight waves on a single word)
-			uint32_t selbits = 0, wave_n = 0;
+			// Which of its 32 keys a thread keeps is compares only; ONE popcount gives its count, one prefix sum over the wave and ONE LDS
+			// atomic per wave and batch its base (a ballot and a popcount per KEY, once to count and once to place, were ~15 vector
+			// instructions per streamed key for one key kept in eight).  The selection lands thread-major inside a wave: any order will
+			// do, bucket_rank ranks by (key, id) and the ids are unique.
+			uint32_t selbits = 0;
 #pragma unroll
 			for (int u = 0; u < SW; u++) {
 				const uint32_t kk[4] = { kq[u].x, kq[u].y, kq[u].z, kq[u].w };
@@ -511,25 +542,24 @@ __global__ void __launch_bounds__(GS_THREADS, 6) slab_sort_kernel(SlabSortArgs a
 					const bool have = el >= off && el < n_el, sel = have && kk[e] >= lo && (open_top || kk[e] < hi);
 					my_below += (have && kk[e] < lo) ? 1u : 0u;
 					selbits |= sel ? 1u << (4 * u + e) : 0u;
-					wave_n += (uint32_t)__popcll(__ballot(sel));
 				}
 			}
+			const uint32_t mine = (uint32_t)__popc(selbits), incl = wave_incl_scan_dpp_u32(mine);
+			const uint32_t wave_n = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
 			if (wave_n != 0u) {      // wave-uniform
-				uint32_t at0 = 0;
-				if (lane == 0) at0 = atomicAdd(&s.nsel, wave_n);
-				at0 = __shfl(at0, 0, WAVE);
-				uint32_t run = 0;
+				uint32_t at = 0;
+				if (lane == 0) at = atomicAdd(&s.nsel, wave_n);
+				at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at) + incl - mine;      // lane 0's: the whole wave is active here
 #pragma unroll
 				for (int u = 0; u < SW; u++) {
+					if (((selbits >> (4 * u)) & 15u) == 0u) continue;
 					const uint32_t kk[4] = { kq[u].x, kq[u].y, kq[u].z, kq[u].w };
 #pragma unroll
 					for (int e = 0; e < 4; e++) {
-						const bool sel = (selbits >> (4 * u + e)) & 1u;
-						const uint64_t m = __ballot(sel);
-						if (m == 0ull) continue;      // wave-uniform
-						const uint32_t at = at0 + run + (uint32_t)__popcll(m & lt);
-						if (sel && at < (uint32_t)GS_NMAX) { s.a[at] = kk[e]; s.b[at] = (wbase + u * GS_THREADS + tid) * 4u + e - off; }
-						run += (uint32_t)__popcll(m);
+						if ((selbits >> (4 * u + e)) & 1u) {
+							if (at < (uint32_t)GS_NMAX) { s.a[at] = kk[e]; s.b[at] = (wbase + u * GS_THREADS + tid) * 4u + e - off; }
+							at++;
+						}
 					}
 				}
 			}
@@ -730,7 +760,7 @@ int launch_cell_scan(const CellScanArgs& a, hipStream_t stream) {
 }
 int launch_cell_colscan(uint32_t* counts, int nblocks, int ncells, uint32_t* cell_count, hipStream_t stream) {
 	if (ncells == 0) return 0;
-	hipLaunchKernelGGL(cell_colscan_kernel, dim3(ncells), dim3(256), 0, stream, counts, nblocks, ncells, cell_count);
+	hipLaunchKernelGGL(cell_colscan_kernel, dim3(ncells), dim3(256), 0, stream, counts, nblocks, cell_count);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

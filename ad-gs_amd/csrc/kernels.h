@@ -26,7 +26,7 @@ struct PreprocessArgs {
 	float* gacc;                     // v2: [P][GACC_STRIDE] accumulator lines, zeroed here for every visible Gaussian (nullptr: skip)
 	unsigned long long* fine_total;  // v2: reset here; the scan pass adds up fine_touched into it
 	// v2 bucket binning (binning.hip; bucket_count == nullptr: sort-based binning): every visible Gaussian is counted into the
-	// coarse cells it covers -- bucket_count[workgroup][cell], every entry written -- and fine_total is accumulated here (the frame's
+	// coarse cells it covers -- bucket_count[cell * count_row_stride + workgroup], every such entry written -- and fine_total is accumulated here (the frame's
 	// prologue zeroed it)
 	uint32_t* bucket_count;
 	// the frame's configuration word, written into the header of the image state (api.hip: frame_cfg_word): a backward that cannot find
@@ -124,6 +124,9 @@ constexpr int SLAB_TARGET = 3072;       // ... the smallest lg that brings the c
 constexpr int SLAB_TARGET_FOREIGN = 2048;      // ... when the bounds are not the camera's own (sampled by cell_sample; another render's on small images): room for a 2 x misfit
 constexpr int GS_NMAX = 4096;           // entries one slab_sort workgroup sorts at a time inside its CU
 constexpr int MAX_CHUNKS = 16384;       // a frame of more than MAX_CHUNKS x GS_NMAX pairs takes the device-wide sort
+// The counts matrix is cell-major: counts[cell * count_row_stride(nblocks) + workgroup] = pairs of preprocess workgroup `workgroup` in `cell`.
+// A row is padded to a multiple of 4 words, so that cell_colscan's 16-byte loads are aligned; nobody writes the pad words before the scan.
+constexpr size_t count_row_stride(int nblocks) { return ((size_t)nblocks + 3u) & ~(size_t)3u; }
 // pinned host mailbox the device publishes the frame totals to (api.hip: the host polls `seq`)
 // overflow: the totals exceed the capacity the frame's launches were enqueued against; overflow_count: such frames since the mailbox exists
 struct Mailbox { volatile uint32_t seq; uint32_t r_cells; unsigned long long r_fine; uint32_t oversize, n_groups, overflow, overflow_count, max_cell_chunks;      // max_cell_chunks: bucket binning, the fullest slab in units of GS_NMAX entries
@@ -144,7 +147,7 @@ struct CellScanArgs {
 	Mailbox* box; uint32_t seq;         // non-null: publish the totals here (a host that waits for them before it enqueues the binning)
 };
 int launch_cell_scan(const CellScanArgs& a, hipStream_t stream);
-int launch_cell_colscan(uint32_t* counts, int nblocks, int ncells, uint32_t* cell_count, hipStream_t stream);
+int launch_cell_colscan(uint32_t* counts /* cell-major, 16-byte aligned */, int nblocks, int ncells, uint32_t* cell_count, hipStream_t stream);
 // rec_key[pos] = depth bits, rec_im[pos] = (Gaussian id, rectangle mask): a cell's unsorted records, struct-of-arrays (slab_sort streams the keys alone)
 int launch_cell_scatter(int P, const uint4* dupinfo, const uint32_t* cell_start, const uint32_t* counts, uint32_t* rec_key, uint2* rec_im, uint32_t cap,
 	int cell_tiles, int cgx, int ncells, uint32_t* pool_cursor, uint32_t* slow_list, hipStream_t stream);      // slow_list[0] <- 0

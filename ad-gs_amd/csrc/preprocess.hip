@@ -193,14 +193,15 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreprocessArgs a) {
 	if (a.bucket_count) {
 		// bucket binning (binning.hip): no scan pass runs.  The pair counts per coarse cell were summed in LDS (the Gaussians of an
 		// object are neighbours in index AND on the screen: global atomics serialise on a few hot cells) and go out as this
-		// workgroup's row of the counts matrix; the fine-tile total (capacity bound of the chunk pool) is one atomic per workgroup.
+		// workgroup's COLUMN of the cell-major counts matrix (counts[cell * count_row_stride + workgroup]: cell_colscan reads a cell's row
+		// contiguously); the fine-tile total (capacity bound of the chunk pool) is one atomic per workgroup.
 		__shared__ uint32_t s_red[256 / WAVE];
 		uint32_t nf = o.nfine;
 #pragma unroll
 		for (int off = WAVE / 2; off > 0; off >>= 1) nf += __shfl_xor(nf, off, WAVE);
 		if ((threadIdx.x & (WAVE - 1)) == 0) s_red[threadIdx.x / WAVE] = nf;
 		__syncthreads();
-		for (int c = threadIdx.x; c < a.cgx * a.cgy; c += 256) a.bucket_count[(size_t)blockIdx.x * (a.cgx * a.cgy) + c] = s_cell[c];
+		for (int c = threadIdx.x; c < a.cgx * a.cgy; c += 256) a.bucket_count[(size_t)c * count_row_stride((int)gridDim.x) + blockIdx.x] = s_cell[c];
 		if (threadIdx.x == 0) {
 			uint32_t n = 0;
 #pragma unroll
