@@ -112,6 +112,10 @@ struct GeomStateV2 {
 	// the device-side (pairs, overflow, ...) words -- then the cell starts, the frame's snapshot of the slab bounds and the counts matrix
 	uint32_t* counters; uint32_t* cell_start; uint2* cell_work; uint32_t* bounds; uint32_t* counts;      // counts[ncells][count_row_stride(ceil(P / 256))]: pairs per (cell, preprocess workgroup), cell-major; bounds[ncells][SLAB_ROW]; cell_work[ncells + 1]
 	static constexpr size_t COUNTER_WORDS = MAX_CELLS + 2 * SCAN_AUX_SLOTS + 8;
+	// the frame's "published" mask (one byte per Gaussian: zeroed by preprocess_fwd, set by the training blend for every id it hands to the
+	// backward's replay lists, read by the preprocess backward: PreprocessBwdArgs::published).  Inside the geometry state, at a place that does
+	// not depend on the carve's options: a backward over copied state buffers finds it
+	uint8_t* published;
 	uint32_t* cell_count() const { return counters; }
 	unsigned long long* bucket_fine_total() const { return reinterpret_cast<unsigned long long*>(counters + MAX_CELLS); }
 	uint32_t* d_counts() const { return counters + MAX_CELLS + 2 * SCAN_AUX_SLOTS; }
@@ -126,6 +130,7 @@ struct GeomStateV2 {
 		g.gacc = c.take<float>(P * GACC_STRIDE);
 		g.dupinfo = c.take<uint4>(P);
 		g.clamped = c.take<uint8_t>(P);
+		g.published = c.take<uint8_t>(P);
 		g.cells_touched = c.take<uint32_t>(P + 1);
 		g.offsets = c.take<uint32_t>(P + 1);
 		g.fine_touched = c.take<uint32_t>(P + 1);
@@ -365,20 +370,22 @@ static OrderHints* order_hints() {
 // found": the backward then carves by today's environment and zeroes the accumulator lines itself -- it never trusts a stale entry.
 // tile_order / sh_staging / timeline: the backward's own measurement knobs (ADGS_TILE_ORDER, ADGS_NO_SH_STAGING, ADGS_TIMELINE_BWD), read by the FORWARD
 // antialiasing: the forward ran the opacity-compensated 2D filter (adgs_raster_options) -- its backward differentiates through it, whatever it is asked
-struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; int antialiasing = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
+struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; int antialiasing = 0; int published = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
 // FrameCfg <-> the configuration word in the image state's header (kernels.h: PreprocessArgs::cfg_word): magic 0xAD6 in bits 20..31, flags v2 /
-// tile_order / sh_staging / timeline / order_ready in bits 19..15, antialiasing in bit 14, ppl (1, 2 or 4) in bits 8..13, cell_tiles in bits 0..7.
-// (Until the filter existed ppl had bits 8..14; every word a library of that layout wrote reads the same here, bit 14 was always 0.)
+// tile_order / sh_staging / timeline / order_ready in bits 19..15, antialiasing in bit 14, published in bit 13, ppl (1, 2 or 4) in bits 8..12,
+// cell_tiles in bits 0..7.  (Until the filter existed ppl had bits 8..14, until the published mask bits 8..13; every word a library of those
+// layouts wrote reads the same here: bits 13 and 14 were always 0 -- such a state carries no mask, and its backward reads every Gaussian.)
+// published: the training blend of this forward wrote GeomStateV2::published AND the backward is to use it (ADGS_PUBLISHED_MASK, read by the FORWARD)
 static uint32_t frame_cfg_word(const FrameCfg& c) {
 	return 0xAD600000u | ((uint32_t)(c.v2 & 1) << 19) | ((uint32_t)(c.tile_order & 1) << 18) | ((uint32_t)(c.sh_staging & 1) << 17) | ((uint32_t)(c.timeline & 1) << 16) |
-	       ((uint32_t)(c.order_ready & 1) << 15) | ((uint32_t)(c.antialiasing & 1) << 14) |
-	       ((uint32_t)(c.ppl & 0x3f) << 8) | (uint32_t)(c.cell_tiles & 0xff);
+	       ((uint32_t)(c.order_ready & 1) << 15) | ((uint32_t)(c.antialiasing & 1) << 14) | ((uint32_t)(c.published & 1) << 13) |
+	       ((uint32_t)(c.ppl & 0x1f) << 8) | (uint32_t)(c.cell_tiles & 0xff);
 }
 static bool frame_cfg_from_word(uint32_t w, FrameCfg* c) {
 	if ((w & 0xFFF00000u) != 0xAD600000u) return false;
-	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x3fu) };
+	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x1fu) };
 	c->tile_order = (int)((w >> 18) & 1u); c->sh_staging = (int)((w >> 17) & 1u); c->timeline = (int)((w >> 16) & 1u); c->order_ready = (int)((w >> 15) & 1u);
-	c->antialiasing = (int)((w >> 14) & 1u);
+	c->antialiasing = (int)((w >> 14) & 1u); c->published = (int)((w >> 13) & 1u);
 	return c->cell_tiles >= 1 && (c->ppl == 1 || c->ppl == 2 || c->ppl == 4);
 }
 struct FrameKey {
@@ -597,6 +604,9 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 			order_tiles = wtiles >= 2048 && fcfg.tile_order;
 			if (!training) order_tiles = false;      // no backward to balance, and an evaluation render does not come back to its camera
 			fcfg.order_ready = order_tiles ? 1 : 0;
+			// the training blend always writes the published mask; ADGS_PUBLISHED_MASK=0 makes this frame's backward ignore it (A/B runs and the
+			// equality tests) -- read here like the backward's other knobs: a backward never reads the environment
+			fcfg.published = (training && env_int("ADGS_PUBLISHED_MASK", 1) != 0) ? 1 : 0;
 			if (training) remember_frame(FrameKey{ ich, gch, width, height, P }, fcfg);
 			frame_word = frame_cfg_word(fcfg);
 		}
@@ -644,6 +654,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 		pa.bucket_count = nullptr;
 		pa.cfg_word = img.header; pa.cfg_value = frame_word;
 		pa.ddir = geom.ddir;      // raw-SH path: the backward will not read the `rest` rows a second time
+		pa.published = training ? geom.published : nullptr;      // zeroed beside `clamped`; the blend (every blend of this call) sets the bytes
 		pa.antialias = antialiasing ? 1 : 0;
 		// bucket binning accumulates the fine-tile total and a few device words, and splits its cells by a snapshot of slab bounds (the
 		// camera's own, else the thread's latest): zeroed / copied by the sh0 kernel on the raw-SH path (no launch of its own), by bin_prepare otherwise
@@ -803,7 +814,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 			ra.order_mode = fwd_order_mode == 2 ? 1 : fwd_order_mode; ra.fwd_order = nullptr;
 			ra.fwd_view = viewmatrix; ra.fwd_sig = nullptr;
 			if (hint_read) { ra.order_mode = 2; ra.fwd_order = hint_read; ra.fwd_sig = reinterpret_cast<const float*>(hint_read + wtiles); }
-			ra.overflow_flag = overflow_flag; ra.publish = training;
+			ra.overflow_flag = overflow_flag; ra.publish = training; ra.published = training ? geom.published : nullptr;
 			{ StageTimer t(ST_RENDER_FWD, stream);
 			  if (launch_render_fwd_v2(ra, stream) != 0) return -1;
 			  for (int c0 = 1; ra.has_sem && c0 < D_S; c0 += 4) {      // semantic channels beyond the Splat's slot: a replay of the published lists
@@ -905,7 +916,7 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 	pa.v2 = 0; pa.dupinfo = nullptr; pa.fine_touched = nullptr; pa.cell_tiles = 1; pa.cgx = gx; pa.cgy = gy;
 	memset(&pa.sh_src, 0, sizeof(pa.sh_src)); pa.sh0 = nullptr; pa.gacc = nullptr; pa.fine_total = nullptr;
 	pa.bucket_count = nullptr;
-	pa.cfg_word = img.header; pa.cfg_value = frame_word; pa.ddir = nullptr;
+	pa.cfg_word = img.header; pa.cfg_value = frame_word; pa.ddir = nullptr; pa.published = nullptr;
 	pa.antialias = antialiasing ? 1 : 0;
 	if (sh_src) { set_error("the raw-SH entry points need the default (v2) pipeline (not ADGS_RASTER_MODE=classic, D_S <= ADGS_V2_MAX_SEMANTIC)"); return -1; }
 	{ StageTimer t(ST_PREPROCESS, stream); if (launch_preprocess_fwd(pa, stream) != 0) return -1; }
@@ -1076,6 +1087,9 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		pa.sh_staging = cfg.sh_staging;
 		pa.ddir = geom.ddir;
 		pa.antialias = cfg.antialiasing;
+		// the forward's published mask, if this state carries one (the frame table, or the header word of copied buffers, says so): the
+		// blend backward above only added to the lines of Gaussians whose byte is set
+		pa.published = cfg.published ? geom.published : nullptr;
 		{ StageTimer t(ST_PREPROCESS_BWD, stream); if (launch_preprocess_bwd(pa, stream) != 0) return -1; }
 		ADGS_LAUNCH_CHECK(debug, stream);
 		return 0;
@@ -1119,7 +1133,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 	memset(&pa.sh_src, 0, sizeof(pa.sh_src)); pa.sh_dst = ShGradDst{};
 	pa.gacc = nullptr; pa.splats = nullptr; pa.W = width; pa.H = height; pa.out_mean2D = nullptr; pa.out_conic = nullptr; pa.out_opacity = nullptr; pa.out_color = nullptr; pa.out_depth = nullptr;
 	pa.out_flow = nullptr; pa.out_sem = nullptr; pa.D_S = D_S; pa.out_mean2D_abs = nullptr;
-	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr;
+	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr; pa.published = nullptr;
 	// anti-aliased frame: the blend's atomics left dL/d(effective opacity) in dL_dopacity; the preprocess backward rescales it in place and
 	// reads the effective opacity from the Splat lines
 	pa.antialias = cfg.antialiasing;
@@ -1466,6 +1480,22 @@ extern "C" long long adgs_test_v2_published_entries(const char* img_buffer, int 
 	V2ImageView v;
 	if (!v2_image_view(img_buffer, width, height, &v)) return -1;
 	return sum_tile_words(v.img.tile_consumed, v.wtiles, (hipStream_t)stream_);
+}
+// the published mask and the accumulator lines of a v2 training forward's geometry state (their place does not depend on the carve's options)
+extern "C" long long adgs_test_v2_published_mask(const char* geom_buffer, int P, uint8_t* out_bytes, float* out_lines, void* stream_) {
+	if (!geom_buffer || P <= 0) return -1;
+	const GeomStateV2 g = GeomStateV2::carve(const_cast<char*>(geom_buffer), (size_t)P, nullptr, false);
+	if (out_bytes && hipMemcpyAsync(out_bytes, g.published, (size_t)P, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess) return -1;
+	if (out_lines && hipMemcpyAsync(out_lines, g.gacc, (size_t)P * GACC_STRIDE * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess) return -1;
+	if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess) return -1;
+	return (long long)P;
+}
+extern "C" int adgs_test_v2_geom_offsets(int P, long long* out2) {
+	if (P <= 0 || !out2) return -1;
+	char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);      // never dereferenced: the carve only adds offsets to it
+	const GeomStateV2 g = GeomStateV2::carve(base, (size_t)P, nullptr, false);
+	out2[0] = (long long)(reinterpret_cast<char*>(g.published) - base); out2[1] = (long long)(reinterpret_cast<char*>(g.gacc) - base);
+	return 0;
 }
 // per-tile counters of the last forward: out_consumed / out_scanned receive one uint32 per wave tile (returns the tile count)
 extern "C" long long adgs_test_v2_tile_counters(const char* img_buffer, int width, int height, uint32_t* out_consumed, uint32_t* out_scanned, long long capacity, void* stream_) {

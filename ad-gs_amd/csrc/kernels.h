@@ -38,6 +38,7 @@ struct PreprocessArgs {
 	// != 0: the opacity-compensated 2D filter (anti-aliased splatting): opacity * sqrt(max(det(cov2D) / det(cov2D + 0.3 I), 2.5e-5)) wherever the
 	// opacity is used after the projection; radii and rectangles come from the dilated covariance as before
 	int antialias;
+	uint8_t* published;              // v2 training frame: [P] bytes zeroed here, beside `clamped` (the blend sets them: RenderV2FwdArgs::published); nullptr: none
 };
 
 int launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t stream);
@@ -101,6 +102,11 @@ struct PreprocessBwdArgs {
 	// (v2: the accumulator line; classic: out_opacity, filled by the blend's atomics and rescaled IN PLACE here) is turned into that of the
 	// opacity, and its share through the filter factor joins the 2D covariance gradient.  Classic reads the effective opacity from `splats`.
 	int antialias;
+	// v2, optional: the forward's "published" mask (api.hip: GeomStateV2::published; one byte per Gaussian, zeroed by preprocess_fwd, set to 1 by
+	// render_fwd_v2's flush_chunk for every id that entered a replay chunk).  A Gaussian whose byte is 0 was never replayed by the blend
+	// backward: its accumulator line is all zero and every output row of it is zero -- it is written as zeros WITHOUT reading any of its
+	// inputs.  nullptr: no mask (classic pipeline, a state whose forward wrote none, ADGS_PUBLISHED_MASK=0): every Gaussian is read.
+	const uint8_t* published;
 };
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream);
 
@@ -191,6 +197,7 @@ struct RenderV2FwdArgs {
 	const float* fwd_view; const float* fwd_sig;      // this frame's view matrix / the one the hint was made under (16 floats each): a hint of another pose is ignored
 	const uint32_t* overflow_flag;          // device word: != 0 = the frame does not fit the capacity of this launch (blend nothing)
 	bool publish;                           // true: the training forward; false: nothing is kept for a backward (pool / tile_* / n_contrib are not touched, may be NULL)
+	uint8_t* published;                     // publish: one byte per Gaussian, zeroed by preprocess_fwd -- set to 1 for every id that leaves in a chunk (PreprocessBwdArgs::published)
 };
 int launch_render_fwd_v2(const RenderV2FwdArgs& a, hipStream_t stream);
 

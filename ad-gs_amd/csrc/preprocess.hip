@@ -189,6 +189,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreprocessArgs a) {
 	if (STAGED || a.bucket_count) __syncthreads();
 	if (a.v2 && !a.bucket_count && idx < SCAN_AUX_SLOTS) a.fine_total[idx] = 0ull;     // counters of the scan's side sum (P >= 1 block: always covered)
 	PreOut o = { 0u, 0u };
+	if (idx < a.P && a.published) a.published[idx] = (uint8_t)0;      // the blend sets the bytes of the Gaussians it hands to the backward (render_v2.hip: flush_chunk)
 	if (idx < a.P) o = preprocess_one<STAGED, AA>(a, idx, s_sh, s_cell, in);
 	if (a.bucket_count) {
 		// bucket binning (binning.hip): no scan pass runs.  The pair counts per coarse cell were summed in LDS (the Gaussians of an

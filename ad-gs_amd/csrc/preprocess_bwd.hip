@@ -49,13 +49,17 @@ constexpr int SH_ROW_FULL = 48, SH_ROW_FULL_LDS = 49, SH_ROW_REST = 45;
 
 // Per-Gaussian inputs of the staged v2 kernel, requested with the SH rows (preprocess.hip: PreIn -- the same reasoning: radii -> (visible?)
 // -> position / scale / rotation / opacity / accumulator line / Splat line -> clamp bits are dependent round trips behind the staging
-// barrier otherwise).  Loaded unconditionally at a clamped index; the staged v2 paths that recompute cov3D (gacc != nullptr, no cov3D) use them.
+// barrier otherwise).  Requested at a clamped index, as ONE batch; the staged v2 paths that recompute cov3D (gacc != nullptr, no cov3D) use them.
+// gate / pub (preprocess_bwd_kernel): with the forward's published mask only the lanes whose Gaussian is published request anything -- the others
+// take the zero-row branch, and a line nobody asks for is not fetched (at C3 nine in ten accumulator and Splat lines) -- and the radius is not
+// needed at all (published implies visible).  Without the mask: every lane, as before.
 struct PreBIn { alignas(16) float q[4]; float4 u0, u1, u2, u3, s0, s1; float p[3], s[3], op; int radius; uint8_t clamped; float dd[9]; };
-__device__ __forceinline__ PreBIn load_preb_in(const PreprocessBwdArgs& a, const int idx) {
+__device__ __forceinline__ PreBIn load_preb_in(const PreprocessBwdArgs& a, const int idx, const bool gate, const bool pub) {
 	PreBIn in;
 	const size_t i = (size_t)min(idx, a.P - 1);
 	const bool rs = a.sh_src.scene_xyz != nullptr && (int)i < a.sh_src.Ns;
-	in.radius = a.radii[i];
+	in.radius = gate ? 0 : a.radii[i];
+	if (!pub) return in;      // (never read: the lane is not `vis`)
 	const float* pos = rs ? a.sh_src.scene_xyz : a.means3D;
 	in.p[0] = pos[3 * i]; in.p[1] = pos[3 * i + 1]; in.p[2] = pos[3 * i + 2];
 	const float* sc = rs ? a.sh_src.scene_scaling : a.scales;
@@ -90,15 +94,20 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 	const bool pf = STAGED && a.gacc != nullptr && a.cov3D == nullptr && a.scales != nullptr && a.rotations != nullptr;      // kernel-uniform
 	// the Adam step in place of the store of the `rest` gradient rows (adgs_sh_adam): the rows are assembled in LDS either way
 	const bool adam_rest = STAGED && raw && (a.sh_dst.adam.scene_rest.p != nullptr || a.sh_dst.adam.obj_rest.p != nullptr);      // kernel-uniform
+	// The forward's published mask (PreprocessBwdArgs::published), before anything else: a wave's 64 bytes are one line -- the only dependent
+	// trip in front of the per-Gaussian requests
+	const bool gate = a.gacc != nullptr && a.published != nullptr;      // kernel-uniform
+	bool pub = true;
+	if (gate) pub = idx < a.P && a.published[idx] != 0;
 	PreBIn in;
 	// the forward left d colour / d direction behind (PreprocessArgs.ddir): no second pass over the `rest` rows -- the LDS rows only carry the gradients out
 	const bool have_ddir = STAGED && raw && pf && a.ddir != nullptr && a.D == 3;      // kernel-uniform
 	if (STAGED) {
 		if (raw && have_ddir) {
-			in = load_preb_in(a, idx);
+			in = load_preb_in(a, idx, gate, pub);
 		} else if (raw) {
 			stage_rows<true, ADGS_PREB_STAGE_U4>(s_sh, SH_ROW_REST, SH_ROW_REST, base, nvalid, a.sh_src.Ns, a.sh_src.scene_rest, a.sh_src.obj_rest, tid, BW_THREADS,
-				[&]() { if (pf) in = load_preb_in(a, idx); });
+				[&]() { if (pf) in = load_preb_in(a, idx, gate, pub); });
 		} else {
 			// materialised [P,16,3] SH tensor: all 12 quads of a thread requested before the first LDS store (preprocess.hip)
 			const float4* src = reinterpret_cast<const float4*>(a.shs + (size_t)base * SH_ROW_FULL);
@@ -107,7 +116,7 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 			float4 v[NQ4];
 #pragma unroll
 			for (int u = 0; u < NQ4; u++) v[u] = ld_stream4(src + min(tid + u * BW_THREADS, total4 - 1));
-			if (pf) in = load_preb_in(a, idx);
+			if (pf) in = load_preb_in(a, idx, gate, pub);
 #pragma unroll
 			for (int u = 0; u < NQ4; u++) {
 				const int q = tid + u * BW_THREADS;
@@ -121,7 +130,8 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 		if (!have_ddir) __syncthreads();      // (with ddir nothing was staged: every thread only ever touches its own LDS row until the closing barrier)
 	}
 	const bool valid = idx < a.P;
-	const bool vis = valid && ((pf ? in.radius : a.radii[idx]) > 0);
+	// published implies radii > 0 (the blend only sees Gaussians the forward preprocess kept): with the mask the radius is not read
+	const bool vis = valid && (gate ? pub : (pf ? in.radius : a.radii[idx]) > 0);
 	// raw scene geometry (preprocess.hip): position / log-scale / raw rotation / opacity logit of Gaussians idx < Ns come from the raw
 	// tensors, and their gradients -- chain rule through exp / normalize / sigmoid included -- go to the raw tensors' gradients
 	const bool rs = a.sh_src.scene_xyz != nullptr && idx < a.sh_src.Ns;

@@ -270,7 +270,17 @@ __global__ void __launch_bounds__(WAVE) render_fwd_v2_kernel(RenderV2FwdArgs a) 
 		blk_next++; blk_left--;
 		uint32_t* c = a.pool + (size_t)chunk * CHUNK_WORDS;
 		const uint32_t mine = s_pub[lane], behind = s_pub[WAVE + lane];
-		if ((uint32_t)lane < cnt) c[lane] = mine;
+		if ((uint32_t)lane < cnt) {
+			c[lane] = mine;
+			// the frame's "published" mask: the preprocess backward reads nothing of a Gaussian no chunk names (its accumulator line stays
+			// zero).  A plain store of the constant 1 into the Gaussian's own byte: one more memory instruction per chunk, nothing to wait for.
+			// Tiles on several XCDs write bytes of one 64-byte line (and the same byte): each L2 keeps the bytes IT wrote dirty and writes back
+			// only those when the kernel ends, so the copies merge in memory byte by byte, and writers of the same byte agree on the value; no
+			// kernel reads the mask before that write-back (preprocess_fwd zeroed it kernels ago, the preprocess backward reads it kernels later).
+			// (One BIT per Gaussian set with an atomic OR was measured first: the atomics of a frame meet in P / 32 words -- +17 us on this
+			// kernel at C2, +9 us at C1: EXPERIMENTS.md.)
+			a.published[mine] = (uint8_t)1;
+		}
 		if (lane == 0) { c[CHUNK_PREV] = prev_chunk; c[CHUNK_COUNT] = cnt; }
 		prev_chunk = chunk;
 		s_pub[lane] = behind;                     // (a partial chunk is the tile's last: what moves down then is never read)

@@ -30,6 +30,14 @@ long long adgs_test_v2_tile_counters(const char* img_buffer, int width, int heig
 long long adgs_test_v2_blend_batches(const char* img_buffer, int width, int height, void* stream);
 /* (start, end) of every coarse cell's depth-sorted candidate list (host array of 2 x `capacity` uint32); returns the number of cells. */
 long long adgs_test_v2_cell_ranges(const char* img_buffer, int width, int height, uint32_t* out_ranges, long long capacity, void* stream);
+/* The "published" mask of a default-pipeline training forward's geometry state (one byte per Gaussian: 1 when the blend handed the id to
+ * the backward's replay lists, else 0) and the accumulator lines ([P][16] floats) as they stand -- after a backward: what the blend backward
+ * summed.  out_bytes: host array of P bytes, out_lines: host array of 16 P floats; either may be NULL.  Returns P, -1 on an error.
+ * Synchronises the stream. */
+long long adgs_test_v2_published_mask(const char* geom_buffer, int P, uint8_t* out_bytes, float* out_lines, void* stream);
+/* Byte offsets of the published mask (out2[0]) and of the accumulator lines (out2[1]) inside a default-pipeline geometry state of P
+ * Gaussians: a test overwrites lines the backward must not read.  Host only.  Returns 0, -1 on a bad argument. */
+int adgs_test_v2_geom_offsets(int P, long long* out2);
 
 /* sizeof of the structs that cross the ABI by pointer (0 adgs_sh_source, 1 adgs_sh_grads, 2 adgs_frame_stats, 3 adgs_frame_status,
  * 4 adgs_func_eval, 5 adgs_adam_group, 6 adgs_sh_adam, 7 adgs_raster_options, 8 adgs_adam_rows, 9 adgs_raster_backward_options,
