@@ -370,22 +370,24 @@ static OrderHints* order_hints() {
 // found": the backward then carves by today's environment and zeroes the accumulator lines itself -- it never trusts a stale entry.
 // tile_order / sh_staging / timeline: the backward's own measurement knobs (ADGS_TILE_ORDER, ADGS_NO_SH_STAGING, ADGS_TIMELINE_BWD), read by the FORWARD
 // antialiasing: the forward ran the opacity-compensated 2D filter (adgs_raster_options) -- its backward differentiates through it, whatever it is asked
-struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; int antialiasing = 0; int published = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
+struct FrameCfg { int v2; int cell_tiles; int ppl; int tile_order = 1; int sh_staging = 1; int timeline = 0; int order_ready = 0; int backwards = 0; int antialiasing = 0; int published = 0; int prefill = 0; };      // order_ready: the forward already built img.tile_order      // backwards: how many backward passes have consumed this forward's accumulator lines
 // FrameCfg <-> the configuration word in the image state's header (kernels.h: PreprocessArgs::cfg_word): magic 0xAD6 in bits 20..31, flags v2 /
-// tile_order / sh_staging / timeline / order_ready in bits 19..15, antialiasing in bit 14, published in bit 13, ppl (1, 2 or 4) in bits 8..12,
-// cell_tiles in bits 0..7.  (Until the filter existed ppl had bits 8..14, until the published mask bits 8..13; every word a library of those
-// layouts wrote reads the same here: bits 13 and 14 were always 0 -- such a state carries no mask, and its backward reads every Gaussian.)
+// tile_order / sh_staging / timeline / order_ready in bits 19..15, antialiasing in bit 14, published in bit 13, prefill in bit 12, ppl (1, 2 or 4) in bits 8..10,
+// cell_tiles in bits 0..7; bit 11 is free.  (Until the filter existed ppl had bits 8..14, until the published mask bits 8..13, until the gradient
+// prefill bits 8..12; every word a library of those layouts wrote reads the same here: bits 11 .. 14 were always 0 -- such a state carries no
+// mask, and its backward reads every Gaussian and writes every zero row itself.)
+// prefill: the backward writes the zero rows of its sparse groups beside the blend backward (grad_prefill.h; ADGS_GRAD_PREFILL, read by the FORWARD)
 // published: the training blend of this forward wrote GeomStateV2::published AND the backward is to use it (ADGS_PUBLISHED_MASK, read by the FORWARD)
 static uint32_t frame_cfg_word(const FrameCfg& c) {
 	return 0xAD600000u | ((uint32_t)(c.v2 & 1) << 19) | ((uint32_t)(c.tile_order & 1) << 18) | ((uint32_t)(c.sh_staging & 1) << 17) | ((uint32_t)(c.timeline & 1) << 16) |
 	       ((uint32_t)(c.order_ready & 1) << 15) | ((uint32_t)(c.antialiasing & 1) << 14) | ((uint32_t)(c.published & 1) << 13) |
-	       ((uint32_t)(c.ppl & 0x1f) << 8) | (uint32_t)(c.cell_tiles & 0xff);
+	       ((uint32_t)(c.prefill & 1) << 12) | ((uint32_t)(c.ppl & 0x7) << 8) | (uint32_t)(c.cell_tiles & 0xff);
 }
 static bool frame_cfg_from_word(uint32_t w, FrameCfg* c) {
 	if ((w & 0xFFF00000u) != 0xAD600000u) return false;
-	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x1fu) };
+	*c = FrameCfg{ (int)((w >> 19) & 1u), (int)(w & 0xffu), (int)((w >> 8) & 0x7u) };
 	c->tile_order = (int)((w >> 18) & 1u); c->sh_staging = (int)((w >> 17) & 1u); c->timeline = (int)((w >> 16) & 1u); c->order_ready = (int)((w >> 15) & 1u);
-	c->antialiasing = (int)((w >> 14) & 1u); c->published = (int)((w >> 13) & 1u);
+	c->antialiasing = (int)((w >> 14) & 1u); c->published = (int)((w >> 13) & 1u); c->prefill = (int)((w >> 12) & 1u) & c->published;
 	return c->cell_tiles >= 1 && (c->ppl == 1 || c->ppl == 2 || c->ppl == 4);
 }
 struct FrameKey {
@@ -607,6 +609,8 @@ static int raster_forward_impl(const ShSource* sh_src, bool training, int antial
 			// the training blend always writes the published mask; ADGS_PUBLISHED_MASK=0 makes this frame's backward ignore it (A/B runs and the
 			// equality tests) -- read here like the backward's other knobs: a backward never reads the environment
 			fcfg.published = (training && env_int("ADGS_PUBLISHED_MASK", 1) != 0) ? 1 : 0;
+			// ADGS_GRAD_PREFILL=0: this frame's backward writes every zero row in the preprocess backward, as before the fill existed (A/B runs, tests)
+			fcfg.prefill = (fcfg.published && env_int("ADGS_GRAD_PREFILL", 1) != 0) ? 1 : 0;
 			if (training) remember_frame(FrameKey{ ich, gch, width, height, P }, fcfg);
 			frame_word = frame_cfg_word(fcfg);
 		}
@@ -1038,36 +1042,6 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		ra.gacc = geom.gacc;
 		ra.tile_order = nullptr;
 		ra.tl_start = cfg.timeline ? img.tile_scanned : nullptr; ra.tl_end = img.tile_batches;      // experiment build only
-		{
-			StageTimer t(ST_RENDER_BWD, stream);
-			if (wtiles >= 2048 && cfg.tile_order) {      // fewer tiles than wave slots: nothing to balance
-				// the forward built the order behind its blend kernel (order_ready); a state from a library build that did not: here
-				if (!cfg.order_ready && launch_tile_order((int)wtiles, img.tile_consumed, img.tile_order, stream) != 0) return -1;
-				ra.tile_order = img.tile_order;
-			}
-			// geom.gacc lines of the visible Gaussians were zeroed by the forward preprocess: the FIRST backward over a forward
-			// accumulates into them as they are.  A second backward over the same forward state (retain_graph) -- or one whose
-			// forward has dropped out of the frame table -- gets them zeroed again here (64 B per Gaussian: the preprocess
-			// backward used to re-zero every line after reading it, 64 MB of writes per frame at C3 for a case that is rare).
-			if (note_backward(fkey) != 0) ADGS_HIP_CHECK(hipMemsetAsync(geom.gacc, 0, (size_t)P * GACC_STRIDE * sizeof(float), stream));
-			ra.sem_src = nullptr; ra.sem_dst = nullptr; ra.sem_stride = 0;
-			if (binning_buffer && launch_render_bwd_v2(ra, stream) != 0) return -1;
-			if (binning_buffer && ra.do_sem && D_S > 1) {
-				// channels 1 .. D_S-1: dL/dalpha is linear in the channels, so each channel's replay adds its share of the geometric
-				// sums to the gacc lines and its own sum_k alpha_k T_k dL/dS to dL_dsemantic[:, c] (zeroed here; channel 0 is written
-				// by the preprocess backward with every other output row)
-				ADGS_HIP_CHECK(hipMemsetAsync(dL_dsemantic, 0, (size_t)P * D_S * sizeof(float), stream));
-				RenderV2BwdArgs rc = ra;
-				rc.do_color = rc.do_flow = rc.do_depth = rc.do_opacity = false; rc.do_sem = true; rc.absgrad = false;      // (refused above when asked for)
-				rc.dL_dpix = nullptr; rc.dL_dpix_depth = nullptr; rc.dL_dpix_flow = nullptr; rc.dL_dpix_opacity = nullptr;
-				rc.bg_image = nullptr; rc.dL_dbg_image = nullptr; rc.sem_stride = D_S;
-				for (int c = 1; c < D_S; c++) {
-					rc.dL_dpix_sem = dL_dpix_semantic + (size_t)c * npix; rc.sem_src = semantic + c; rc.sem_dst = dL_dsemantic + c;
-					if (launch_render_bwd_v2(rc, stream) != 0) return -1;
-				}
-			}
-		}
-		ADGS_LAUNCH_CHECK(debug, stream);
 		PreprocessBwdArgs pa;
 		pa.P = P; pa.D = D; pa.M = M;
 		pa.means3D = means3D; pa.radii = radii; pa.shs = shs; pa.clamped = geom.clamped;
@@ -1090,6 +1064,41 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 		// the forward's published mask, if this state carries one (the frame table, or the header word of copied buffers, says so): the
 		// blend backward above only added to the lines of Gaussians whose byte is set
 		pa.published = cfg.published ? geom.published : nullptr;
+		// the zero rows of the sparse groups (grad_prefill.h): collected here, where every destination is known, and written by fill workgroups
+		// inside the blend backward's grid below -- or by a launch of their own when this backward has no blend backward
+		pa.prefill = (cfg.prefill && cfg.published) ? 1 : 0;
+		const FillPlan fill = preprocess_bwd_fill_plan(pa);
+		{
+			StageTimer t(ST_RENDER_BWD, stream);
+			if (wtiles >= 2048 && cfg.tile_order) {      // fewer tiles than wave slots: nothing to balance
+				// the forward built the order behind its blend kernel (order_ready); a state from a library build that did not: here
+				if (!cfg.order_ready && launch_tile_order((int)wtiles, img.tile_consumed, img.tile_order, stream) != 0) return -1;
+				ra.tile_order = img.tile_order;
+			}
+			// geom.gacc lines of the visible Gaussians were zeroed by the forward preprocess: the FIRST backward over a forward
+			// accumulates into them as they are.  A second backward over the same forward state (retain_graph) -- or one whose
+			// forward has dropped out of the frame table -- gets them zeroed again here (64 B per Gaussian: the preprocess
+			// backward used to re-zero every line after reading it, 64 MB of writes per frame at C3 for a case that is rare).
+			if (note_backward(fkey) != 0) ADGS_HIP_CHECK(hipMemsetAsync(geom.gacc, 0, (size_t)P * GACC_STRIDE * sizeof(float), stream));
+			ra.sem_src = nullptr; ra.sem_dst = nullptr; ra.sem_stride = 0;
+			if (binning_buffer && launch_render_bwd_v2(ra, stream, pa.prefill ? &fill : nullptr) != 0) return -1;
+			if (!binning_buffer && pa.prefill && launch_grad_prefill(fill, stream) != 0) return -1;
+			if (binning_buffer && ra.do_sem && D_S > 1) {
+				// channels 1 .. D_S-1: dL/dalpha is linear in the channels, so each channel's replay adds its share of the geometric
+				// sums to the gacc lines and its own sum_k alpha_k T_k dL/dS to dL_dsemantic[:, c] (zeroed here; channel 0 is written
+				// by the preprocess backward with every other output row)
+				ADGS_HIP_CHECK(hipMemsetAsync(dL_dsemantic, 0, (size_t)P * D_S * sizeof(float), stream));
+				RenderV2BwdArgs rc = ra;
+				rc.do_color = rc.do_flow = rc.do_depth = rc.do_opacity = false; rc.do_sem = true; rc.absgrad = false;      // (refused above when asked for)
+				rc.dL_dpix = nullptr; rc.dL_dpix_depth = nullptr; rc.dL_dpix_flow = nullptr; rc.dL_dpix_opacity = nullptr;
+				rc.bg_image = nullptr; rc.dL_dbg_image = nullptr; rc.sem_stride = D_S;
+				for (int c = 1; c < D_S; c++) {
+					rc.dL_dpix_sem = dL_dpix_semantic + (size_t)c * npix; rc.sem_src = semantic + c; rc.sem_dst = dL_dsemantic + c;
+					if (launch_render_bwd_v2(rc, stream) != 0) return -1;
+				}
+			}
+		}
+		ADGS_LAUNCH_CHECK(debug, stream);
 		{ StageTimer t(ST_PREPROCESS_BWD, stream); if (launch_preprocess_bwd(pa, stream) != 0) return -1; }
 		ADGS_LAUNCH_CHECK(debug, stream);
 		return 0;
@@ -1133,7 +1142,7 @@ static int raster_backward_impl(const ShSource* sh_src, const ShGradDst* sh_dst,
 	memset(&pa.sh_src, 0, sizeof(pa.sh_src)); pa.sh_dst = ShGradDst{};
 	pa.gacc = nullptr; pa.splats = nullptr; pa.W = width; pa.H = height; pa.out_mean2D = nullptr; pa.out_conic = nullptr; pa.out_opacity = nullptr; pa.out_color = nullptr; pa.out_depth = nullptr;
 	pa.out_flow = nullptr; pa.out_sem = nullptr; pa.D_S = D_S; pa.out_mean2D_abs = nullptr;
-	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr; pa.published = nullptr;
+	pa.sh_staging = cfg.sh_staging; pa.ddir = nullptr; pa.published = nullptr; pa.prefill = 0;
 	// anti-aliased frame: the blend's atomics left dL/d(effective opacity) in dL_dopacity; the preprocess backward rescales it in place and
 	// reads the effective opacity from the Splat lines
 	pa.antialias = cfg.antialiasing;

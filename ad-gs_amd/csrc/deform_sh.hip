@@ -186,6 +186,92 @@ __global__ void __launch_bounds__(256) deform_lin_param_grad_kernel(ParamGradArg
 	}
 }
 
+// The same rows for the raster backward of a prefilled frame (grad_prefill.h), by groups of 256 Gaussians of the frame under the published
+// mask: in a SPARSE group the fill has stored the zero rows, and only the rows of the published Gaussians are written -- one row (D * n_params
+// consecutive floats) per wave and store instruction; a DENSE group writes every row as the flat kernel does, 16-byte stores over the group's
+// slab of each side.  Every element is __fmul_rn(w[k], g[m, d]), as there.
+struct ParamGradRowsArgs {
+	int Ns, P, D, gstride;                            // Gaussians [0, Ns): scene side, [Ns, P): object side
+	const float *g_scene, *g_obj;                     // g[m * gstride + d], m counted from the side's first Gaussian
+	float *out_scene, *out_obj;                       // [count, D, n_params] per side; nullptr: that side is not wanted
+	const uint8_t* published;                         // [P]
+	adgs_func_eval f;
+};
+__global__ void __launch_bounds__(PREFILL_GROUP) lin_param_grad_rows_kernel(ParamGradRowsArgs a) {
+	extern __shared__ float s_w[];
+	const int tid = threadIdx.x, base = blockIdx.x * PREFILL_GROUP;
+	const bool pub = base + tid < a.P && a.published[base + tid] != 0;
+	const int npub = __syncthreads_count(pub);
+	const bool sparse = prefill_group_sparse(npub, min(PREFILL_GROUP, a.P - base));      // block-uniform: the rule the fill and the preprocess backward applied to these bytes
+	if (sparse && npub == 0) return;
+	const int np = a.f.n_params, L = a.D * np;
+	for (int k = tid; k < np; k += PREFILL_GROUP) s_w[k] = 0.f;
+	__syncthreads();
+	const int total = a.f.n_terms[0] + a.f.n_terms[1] + a.f.n_terms[2];
+	for (int i = tid; i < total; i += PREFILL_GROUP) s_w[a.f.index[i]] = a.f.weight[i];
+	__syncthreads();
+	if (sparse) {
+		// the group's published Gaussians as a list in LDS (fewer than half of 256), their npub * L outputs dealt to all 256 threads:
+		// consecutive threads on consecutive floats of a row
+		__shared__ int s_list[PREFILL_GROUP];
+		__shared__ int s_wave[PREFILL_GROUP / WAVE];
+		const int lane = tid & (WAVE - 1), w = tid / WAVE;
+		const uint64_t m = __builtin_amdgcn_ballot_w64(pub);
+		if (lane == 0) s_wave[w] = __popcll(m);
+		__syncthreads();
+		int off = 0;
+		for (int i = 0; i < w; i++) off += s_wave[i];
+		if (pub) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = base + tid;
+		__syncthreads();
+		for (int e = tid; e < npub * L; e += PREFILL_GROUP) {
+			const int j = e / L, c = e - j * L, d = c / np, gi = s_list[j];
+			const bool ob = gi >= a.Ns;
+			float* const out = ob ? a.out_obj : a.out_scene;
+			if (!out) continue;
+			const size_t r = ob ? gi - a.Ns : gi;
+			st_stream(out + r * (size_t)L + c, __fmul_rn(s_w[c - d * np], (ob ? a.g_obj : a.g_scene)[r * (size_t)a.gstride + d]));
+		}
+		return;
+	}
+	const int end = min(base + PREFILL_GROUP, a.P);
+#pragma unroll
+	for (int side = 0; side < 2; side++) {
+		const int first = side ? a.Ns : 0, lo = max(base, first), hi = side ? end : min(end, a.Ns);
+		float* const out = side ? a.out_obj : a.out_scene;
+		if (lo >= hi || !out) continue;
+		float* const dst = out + (size_t)(lo - first) * L;
+		const float* const g = (side ? a.g_obj : a.g_scene) + (size_t)(lo - first) * a.gstride;
+		const int n = (hi - lo) * L;                   // <= 256 rows of the group
+		auto elem = [&](int e) {
+			const uint32_t row = (uint32_t)e / (uint32_t)np, m = row / (uint32_t)a.D;
+			return __fmul_rn(s_w[(uint32_t)e - row * (uint32_t)np], g[(size_t)m * a.gstride + (row - m * (uint32_t)a.D)]);
+		};
+		const int head = min(n, (int)((16u - ((uint32_t)reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
+		if (tid < head) dst[tid] = elem(tid);
+		const int n4 = (n - head) >> 2;
+		for (int q = tid; q < n4; q += PREFILL_GROUP) {
+			const int e = head + 4 * q;
+			const uint32_t row0 = (uint32_t)e / (uint32_t)np;
+			int k = (int)((uint32_t)e - row0 * (uint32_t)np);
+			uint32_t m = row0 / (uint32_t)a.D; int d = (int)(row0 - m * (uint32_t)a.D);
+			float gv = g[(size_t)m * a.gstride + d];
+			float v[4];
+#pragma unroll
+			for (int it = 0; it < 4; it++) {
+				v[it] = __fmul_rn(s_w[k], gv);
+				if (++k == np) {
+					k = 0;
+					if (++d == a.D) { d = 0; m++; }
+					if (e + it + 1 < n) gv = g[(size_t)m * a.gstride + d];
+				}
+			}
+			st_stream4(reinterpret_cast<float4*>(dst + e), make_float4(v[0], v[1], v[2], v[3]));
+		}
+		const int tail0 = head + (n4 << 2);
+		if (tail0 + tid < n) dst[tail0 + tid] = elem(tail0 + tid);
+	}
+}
+
 // coefficient 0 of the raw-SH path: sh0[n, c] = dc[n, c] + f_shs(t)(shs_deform_param[n, c, :]).
 // Fast kernel (n_params a multiple of 4, at most 32): one thread per (Gaussian, channel) ROW, which it reads as 16-byte
 // words -- consecutive threads own consecutive rows, so the loads are perfectly coalesced without any staging -- and dots
@@ -325,6 +411,17 @@ int launch_lin_param_grad2(int count_a, const float* g_a, float* out_a, int coun
 	pg.nb0 = two ? (int)nb_a : 0; pg.count_b = two ? count_b : 0; pg.g_b = two ? g_b : nullptr; pg.out_b = two ? out_b : nullptr; pg.adam_b = two ? sb : off;
 	if (sa.p || sb.p) hipLaunchKernelGGL(deform_lin_param_grad_kernel<true>, dim3((unsigned)(nb_a + nb_b)), dim3(256), f.n_params * sizeof(float), stream, pg);
 	else hipLaunchKernelGGL(deform_lin_param_grad_kernel<false>, dim3((unsigned)(nb_a + nb_b)), dim3(256), f.n_params * sizeof(float), stream, pg);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+int launch_lin_param_grad_rows(int Ns, const float* g_scene, float* out_scene, int No, const float* g_obj, float* out_obj, int D, int gstride,
+	const adgs_func_eval& f, const uint8_t* published, hipStream_t stream) {
+	if (f.n_params <= 0) return 0;
+	const bool on_a = out_scene && Ns > 0, on_b = out_obj && No > 0;
+	if (!on_a && !on_b) return 0;
+	if ((on_a && !g_scene) || (on_b && !g_obj) || !published) { set_error("launch_lin_param_grad_rows: NULL gradient buffer or mask"); return -1; }
+	const ParamGradRowsArgs pg = { Ns, Ns + No, D, gstride, g_scene, g_obj, on_a ? out_scene : nullptr, on_b ? out_obj : nullptr, published, f };
+	hipLaunchKernelGGL(lin_param_grad_rows_kernel, dim3((unsigned)((Ns + No + PREFILL_GROUP - 1) / PREFILL_GROUP)), dim3(PREFILL_GROUP), f.n_params * sizeof(float), stream, pg);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "func_eval.h"
+#include "grad_prefill.h"
 
 namespace adgs {
 
@@ -107,8 +108,15 @@ struct PreprocessBwdArgs {
 	// backward: its accumulator line is all zero and every output row of it is zero -- it is written as zeros WITHOUT reading any of its
 	// inputs.  nullptr: no mask (classic pipeline, a state whose forward wrote none, ADGS_PUBLISHED_MASK=0): every Gaussian is read.
 	const uint8_t* published;
+	// != 0 (needs `published` and the v2 accumulator lines): the zero rows of the SPARSE groups of 256 Gaussians (grad_prefill.h) have been
+	// written by the fill of the frame's FillPlan before this launch -- in such a group only the published Gaussians store anything, here and in
+	// the SH-deformation rows behind this kernel.  0: every row of every group is written here, as before.
+	int prefill;
 };
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream);
+// a.prefill != 0: the fill plan of these arguments (every destination and row range of the kernel's zero-row branch and of the SH-deformation
+// rows); the caller runs it BEFORE launch_preprocess_bwd (launch_render_bwd_v2 / launch_grad_prefill).  Otherwise an empty plan.
+FillPlan preprocess_bwd_fill_plan(const PreprocessBwdArgs& a);
 
 // ---- v2 pipeline (render_v2.hip) ----
 constexpr int CHUNK_WORDS = 2 + WAVE;   // [64 Gaussian ids, prev chunk, count]: the ids first, so that a wave reads `c[lane]` and the link words with two
@@ -219,7 +227,10 @@ struct RenderV2BwdArgs {
 	// geometric sums add into the gacc line as in the main pass (dL/dalpha is linear in the channels).  nullptr: the main pass.
 	const float* sem_src; float* sem_dst; int sem_stride;
 };
-int launch_render_bwd_v2(const RenderV2BwdArgs& a, hipStream_t stream);
+// fill (optional): the frame's fill plan -- its workgroups are appended to this launch's grid (grad_prefill.h); a launch without tiles runs them alone
+int launch_render_bwd_v2(const RenderV2BwdArgs& a, hipStream_t stream, const FillPlan* fill = nullptr);
+// the same fill in a launch of its own (a backward without a blend backward)
+int launch_grad_prefill(const FillPlan& plan, hipStream_t stream);
 
 // Forward of the semantic channels 1 .. D_S-1 (channel 0 rides in the Splat and is blended by render_fwd_v2): a back-to-front
 // replay of the chunk lists the main forward published, S = s a + (1 - a) S per contributing entry (the same sum as forward.cu:372
@@ -255,6 +266,10 @@ int launch_lin_param_grad(int count, int D, const float* g, int gstride, float* 
 int launch_lin_param_grad2(int count_a, const float* g_a, float* out_a, int count_b, const float* g_b, float* out_b, int D, int gstride,
 	const adgs_func_eval& f, hipStream_t stream, const AdamSlot* adam_a = nullptr, const AdamSlot* adam_b = nullptr, float beta1 = 0.f, float beta2 = 0.f,
 	float eps = 0.f);
+// The same rows by groups of 256 Gaussians of the frame (scene side [0, Ns), object side [Ns, Ns + No)) under the published mask: a sparse group
+// (grad_prefill.h) gets the rows of its published Gaussians only -- the fill wrote the others --, a dense group every row.  Gradient stores only.
+int launch_lin_param_grad_rows(int Ns, const float* g_scene, float* out_scene, int No, const float* g_obj, float* out_obj, int D, int gstride,
+	const adgs_func_eval& f, const uint8_t* published, hipStream_t stream);
 // lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t), formed in double and rounded once (optim.hip)
 void adam_bias_terms(float lr, int step, float beta1, float beta2, float* step_size, float* inv_bc2_sqrt);
 // sh0[N,3] = dc + f_shs(t); optionally runs the frame's prologue (counters zeroed, slab bounds snapshot) for the binning kernels behind it

@@ -99,6 +99,14 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 	const bool gate = a.gacc != nullptr && a.published != nullptr;      // kernel-uniform
 	bool pub = true;
 	if (gate) pub = idx < a.P && a.published[idx] != 0;
+	// the group rule of grad_prefill.h on the block's 256 bytes: in a SPARSE group the fill has written every zero row before this launch, and
+	// only the published lanes store anything below; a block without one has nothing left to do (the Adam step of the `rest` rows stays dense)
+	bool sparse = false;
+	if (gate && a.prefill) {
+		const int npub = __syncthreads_count(pub);
+		sparse = prefill_group_sparse(npub, nvalid);      // block-uniform
+		if (sparse && npub == 0 && !adam_rest) return;
+	}
 	PreBIn in;
 	// the forward left d colour / d direction behind (PreprocessArgs.ddir): no second pass over the `rest` rows -- the LDS rows only carry the gradients out
 	const bool have_ddir = STAGED && raw && pf && a.ddir != nullptr && a.D == 3;      // kernel-uniform
@@ -135,7 +143,11 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 	// raw scene geometry (preprocess.hip): position / log-scale / raw rotation / opacity logit of Gaussians idx < Ns come from the raw
 	// tensors, and their gradients -- chain rule through exp / normalize / sigmoid included -- go to the raw tensors' gradients
 	const bool rs = a.sh_src.scene_xyz != nullptr && idx < a.sh_src.Ns;
-	if (valid && !vis) {
+	if (valid && !vis && sparse) {
+		// the fill wrote this Gaussian's zero rows (grad_prefill.h): nothing is stored, in global memory or in LDS -- but for the Adam step of
+		// the `rest` rows, which reads every LDS row of the block
+		if (STAGED && raw && adam_rest) for (int i = 0; i < SH_ROW_REST; i++) s_sh[tid * SH_ROW_REST + i] = 0.f;
+	} else if (valid && !vis) {
 		// v2: every output row is written here, so the caller does not have to zero-fill them
 		if (a.gacc) {
 			a.out_mean2D[3 * (size_t)idx] = 0.f; a.out_mean2D[3 * (size_t)idx + 1] = 0.f; a.out_mean2D[3 * (size_t)idx + 2] = 0.f;
@@ -484,6 +496,20 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 			// a Gaussian outside the frustum has a zero gradient row, not no row: Adam moves it by its moments (torch.optim.Adam is dense)
 			adam_rows<4>(s_sh, SH_ROW_REST, SH_ROW_REST, base, nvalid, a.sh_src.Ns, a.sh_dst.adam.scene_rest, a.sh_dst.adam.obj_rest, a.sh_dst.adam.beta1, a.sh_dst.adam.beta2, a.sh_dst.adam.eps,
 				tid, BW_THREADS);
+		} else if (sparse) {
+			// a sparse group: the rows of the published Gaussians only, each wave its own (at most a few dozen of the block's 256 rows; the LDS
+			// rows of the others hold whatever was staged).  One row per store instruction: 180 / 192 consecutive bytes.
+			const int lane = tid & (WAVE - 1), w0 = tid - lane;
+			for (uint64_t m = __builtin_amdgcn_ballot_w64(vis); m != 0ull; m &= m - 1ull) {
+				const int r = w0 + __builtin_ctzll(m), gi = base + r;
+				if (raw) {
+					const bool is_obj = gi >= a.sh_src.Ns;
+					float* const gre = is_obj ? a.sh_dst.obj_rest : a.sh_dst.scene_rest;
+					if (gre && lane < SH_ROW_REST) st_stream(gre + (size_t)(is_obj ? gi - a.sh_src.Ns : gi) * SH_ROW_REST + lane, s_sh[r * SH_ROW_REST + lane]);
+				} else if (lane < SH_ROW_FULL) {
+					st_stream(a.dL_dsh + (size_t)gi * SH_ROW_FULL + lane, s_sh[r * SH_ROW_FULL_LDS + lane]);
+				}
+			}
 		} else if (raw) {
 			stage_rows<false>(s_sh, SH_ROW_REST, SH_ROW_REST, base, nvalid, a.sh_src.Ns, a.sh_dst.scene_rest, a.sh_dst.obj_rest, tid, BW_THREADS);
 		} else {
@@ -498,6 +524,48 @@ __global__ void __launch_bounds__(BW_THREADS) preprocess_bwd_kernel(PreprocessBw
 }
 
 } // namespace
+
+// The destinations of the kernel's zero-row branch (`valid && !vis` above) and of the SH-deformation rows behind it, as the fill plan of a
+// prefilled frame: exactly the arrays and row ranges that branch writes for these arguments -- whoever changes one changes the other.
+FillPlan preprocess_bwd_fill_plan(const PreprocessBwdArgs& a) {
+	FillPlan fp;
+	fp.published = nullptr; fp.P = a.P; fp.n = 0; fp.start = 0u; fp.groups = 0u;
+	if (!a.prefill || !a.gacc || !a.published || a.P <= 0) return fp;
+	fp.published = a.published;
+	const int P = a.P;
+	const bool raw = a.sh_src.scene_dc != nullptr;
+	const int Ns = raw ? max(0, min(a.sh_src.Ns, P)) : 0;                          // raw SH: Gaussians [0, Ns) are the scene side's
+	const int Nr = a.sh_src.scene_xyz ? max(0, min(a.sh_src.Ns, P)) : 0;           // raw scene geometry: rows [0, Nr) belong to the raw tensors
+	auto all = [&](float* p, int row) { fill_plan_add(fp, p, row, row, 0, P); };
+	auto tail = [&](float* p, int row) { if (p) fill_plan_add(fp, p + (size_t)Nr * row, row, row, Nr, P - Nr); };      // the rows `!rs` owns
+	all(a.out_mean2D, 3); all(a.out_mean2D_abs, 3); all(a.out_conic, 4);
+	tail(a.out_opacity, 1);
+	all(a.out_depth, 1); all(a.out_color, 3);
+	tail(a.out_flow, 3);
+	if (a.D_S >= 1) fill_plan_add(fp, a.out_sem, 1, a.D_S, 0, P);                  // channel 0 only
+	if (Nr > 0) {
+		fill_plan_add(fp, a.sh_dst.scene_xyz, 3, 3, 0, Nr); fill_plan_add(fp, a.sh_dst.scene_scaling, 3, 3, 0, Nr);
+		fill_plan_add(fp, a.sh_dst.scene_rotation, 4, 4, 0, Nr); fill_plan_add(fp, a.sh_dst.scene_opacity, 1, 1, 0, Nr);
+	}
+	tail(a.dL_dmean3D, 3);
+	all(a.dL_dcov3D, 6);
+	if (raw) {
+		fill_plan_add(fp, a.sh_dst.scene_dc, 3, 3, 0, Ns); fill_plan_add(fp, a.sh_dst.obj_dc, 3, 3, Ns, P - Ns);
+		all(a.sh_dst.rgb_factor, 3);
+		const bool adam_rest = a.sh_dst.adam.scene_rest.p || a.sh_dst.adam.obj_rest.p;      // the Adam step has no gradient store: its rows stay dense
+		const int rest = (a.M - 1) * 3;
+		if (!adam_rest) { fill_plan_add(fp, a.sh_dst.scene_rest, rest, rest, 0, Ns); fill_plan_add(fp, a.sh_dst.obj_rest, rest, rest, Ns, P - Ns); }
+		const bool adam_sp = a.sh_dst.adam.scene_sp.p || a.sh_dst.adam.obj_sp.p;
+		if (has_lin_host(a.sh_src.f) && !adam_sp) {
+			const int row = 3 * a.sh_src.f.n_params;
+			fill_plan_add(fp, a.sh_dst.scene_sp, row, row, 0, Ns); fill_plan_add(fp, a.sh_dst.obj_sp, row, row, Ns, P - Ns);
+		}
+	} else if (a.shs) {
+		all(a.dL_dsh, a.M * 3);
+	}
+	if (a.scales) { tail(a.dL_dscale, 3); tail(a.dL_drot, 4); }
+	return fp;
+}
 
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream) {
 	if (a.P == 0) return 0;
@@ -526,6 +594,9 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream) {
 	// raw-SH path: d/d(shs_deform_param[m, c, k]) = w_k * dL/d(dc[m, c]) as flat coalesced passes
 	if (raw && has_lin_host(a.sh_src.f)) {
 		const int No = a.P - a.sh_src.Ns;
+		// prefilled frame: by groups under the mask (the Adam instantiation stays flat and dense: it has no gradient store to prefill)
+		if (a.prefill && a.gacc && a.published && !adam_sp)
+			return launch_lin_param_grad_rows(a.sh_src.Ns, a.sh_dst.scene_dc, a.sh_dst.scene_sp, No, a.sh_dst.obj_dc, a.sh_dst.obj_sp, 3, 3, a.sh_src.f, a.published, stream);
 		if (launch_lin_param_grad2(a.sh_src.Ns, a.sh_dst.scene_dc, a.sh_dst.scene_sp, No, a.sh_dst.obj_dc, a.sh_dst.obj_sp, 3, 3, a.sh_src.f, stream,
 		                           &a.sh_dst.adam.scene_sp, &a.sh_dst.adam.obj_sp, a.sh_dst.adam.beta1, a.sh_dst.adam.beta2, a.sh_dst.adam.eps) != 0) return -1;
 	}

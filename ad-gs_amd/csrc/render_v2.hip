@@ -585,7 +585,15 @@ __device__ __forceinline__ uint64_t eval_entry_bwd(const EntryGeom& eg, float py
 // ABS: RenderV2BwdArgs::absgrad -- slots 14 and 15 of the accumulator line receive sum |L (A dx + B dy)| and sum |L (B dx + C dy)|.  A template
 // parameter: the instantiations without it are the code they were before the option existed (same registers, LDS and instruction stream).
 template <int PPL, bool FULL, bool ABS>
-__global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) {
+__global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a, FillPlan fp) {
+	// Fill workgroups of the frame's gradient tensors (grad_prefill.h) ride in this grid: workgroups [fp.start, fp.start + fp.groups) store the
+	// zero rows of one sparse group each and leave -- stores that depend on nothing here, beside a kernel that is VALU-bound.  One wave-uniform
+	// branch; the tile workgroups behind them move up by fp.groups.  fp.groups == 0: no fill (the extra-channel replays, a frame without a plan).
+	uint32_t wg = blockIdx.x;
+	if (wg >= fp.start && fp.groups != 0u) {
+		if (wg - fp.start < fp.groups) { prefill_group(fp, wg - fp.start, (int)threadIdx.x); return; }
+		wg -= fp.groups;
+	}
 	constexpr int ROWS = 4 * PPL;
 	const bool do_color = FULL || a.do_color, do_flow = FULL || a.do_flow, do_sem = FULL || a.do_sem, do_depth = FULL || a.do_depth, do_opacity = FULL || a.do_opacity;
 	// 4096 + 3584 bytes: 21 one-wave workgroups per CU (8768 bytes until round 3 capped the kernel at 18 = 4.5 waves per SIMD whatever
@@ -598,7 +606,7 @@ __global__ void __launch_bounds__(WAVE) render_bwd_v2_kernel(RenderV2BwdArgs a) 
 	constexpr int RROWS = ABS ? RED_ROWS_ABS : RED_ROWS;
 	__shared__ __attribute__((aligned(16))) float s_red[RROWS * RED_STRIDE];
 	const int lane = threadIdx.x;
-	const uint32_t tile = a.tile_order ? a.tile_order[blockIdx.x] : blockIdx.x;
+	const uint32_t tile = a.tile_order ? a.tile_order[wg] : wg;
 	const uint32_t tx = tile % a.gx, ty = tile / a.gx;
 	const uint32_t px = tx * TILE_X + (lane & 15);
 	const uint32_t py0 = ty * ROWS + (lane >> 4);
@@ -943,27 +951,46 @@ int launch_render_sem_fwd_v2(const RenderV2SemFwdArgs& a, hipStream_t stream) {
 }
 
 namespace {
+// the fill of grad_prefill.h in a launch of its own: a backward without a blend backward to ride on (no binning state, no tiles)
+__global__ void __launch_bounds__(WAVE) grad_prefill_kernel(FillPlan fp) {
+	prefill_group(fp, blockIdx.x, (int)threadIdx.x);
+}
 template <bool ABS>
-void launch_render_bwd_v2_t(const RenderV2BwdArgs& a, uint32_t T, bool full, hipStream_t stream) {
+void launch_render_bwd_v2_t(const RenderV2BwdArgs& a, const FillPlan& fp, uint32_t T, bool full, hipStream_t stream) {
 	if (a.ppl == 1) {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<1, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<1, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<1, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<1, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
 	} else if (a.ppl == 2) {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<2, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<2, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<2, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<2, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
 	} else {
-		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<4, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
-		else hipLaunchKernelGGL((render_bwd_v2_kernel<4, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a);
+		if (full) hipLaunchKernelGGL((render_bwd_v2_kernel<4, true, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
+		else hipLaunchKernelGGL((render_bwd_v2_kernel<4, false, ABS>), dim3(T), dim3(WAVE), 0, stream, a, fp);
 	}
 }
 } // namespace
-int launch_render_bwd_v2(const RenderV2BwdArgs& a, hipStream_t stream) {
+int launch_grad_prefill(const FillPlan& plan, hipStream_t stream) {
+	if (!plan.published || plan.n == 0 || plan.P <= 0) return 0;
+	hipLaunchKernelGGL(grad_prefill_kernel, dim3((unsigned)((plan.P + PREFILL_GROUP - 1) / PREFILL_GROUP)), dim3(WAVE), 0, stream, plan);
+	ADGS_HIP_CHECK(hipGetLastError());
+	return 0;
+}
+int launch_render_bwd_v2(const RenderV2BwdArgs& a, hipStream_t stream, const FillPlan* fill) {
 	const uint32_t T = (uint32_t)a.gx * a.gy;
 	const bool full = a.do_color && a.do_flow && a.do_sem && a.do_depth && a.do_opacity && a.dL_dpix_opacity != nullptr && !a.sem_src && !a.sem_dst;
 	// the absolute sums of a pair are not the sum of the absolutes of its per-channel shares: no extra semantic replay may carry them
 	if (a.absgrad && (a.sem_src || a.sem_dst)) { set_error("blend backward: absolute gradient sums cannot be formed by the extra semantic channel replays"); return -1; }
-	if (a.absgrad) launch_render_bwd_v2_t<true>(a, T, full, stream);
-	else launch_render_bwd_v2_t<false>(a, T, full, stream);
+	FillPlan fp;
+	if (fill) fp = *fill; else { fp.published = nullptr; fp.P = 0; fp.n = 0; }
+	fp.start = 0u; fp.groups = 0u;
+	if (fill && fp.published && fp.n > 0 && fp.P > 0) {
+		if (T == 0) return launch_grad_prefill(fp, stream);      // no tile: nothing to ride on
+		fp.groups = (uint32_t)((fp.P + PREFILL_GROUP - 1) / PREFILL_GROUP);
+		fp.start = prefill_start(T);
+	}
+	if (T + fp.groups == 0) return 0;
+	if (a.absgrad) launch_render_bwd_v2_t<true>(a, fp, T + fp.groups, full, stream);
+	else launch_render_bwd_v2_t<false>(a, fp, T + fp.groups, full, stream);
 	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
