@@ -171,6 +171,16 @@ SIGNATURES = {
     "adgs_mesh_keep_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_mesh_normals_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
     "adgs_mesh_vertex_normals": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_geometry.h
+    "adgs_geometry_grid_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_geometry_grid_plan": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_geometry_grid_build": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_geometry_nearest_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_geometry_nearest": (c_i, [c_i, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_geometry_face_areas": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p]),
+    "adgs_geometry_sample": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.c_ulonglong, c_p, c_p, c_p]),
+    "adgs_geometry_stats_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_geometry_distance_stats": (c_i, [c_i, c_p, c_i, c_p, ctypes.c_double, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

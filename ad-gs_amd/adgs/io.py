@@ -2,7 +2,8 @@
 write and read them (scene/gaussian_model.py:413-459, 465-541), so that models trained by either implementation load in the
 other.  The reference goes through the `plyfile` package (not installed here); the binary little-endian PLY it produces --
 one `vertex` element of float32 properties in construct_list_of_attributes order -- is written and parsed directly.
-write_mesh_ply / read_mesh_ply: the triangle mesh adgs.tsdf extracts, as a binary PLY with a face list.
+write_mesh_ply / read_mesh_ply: the triangle mesh adgs.tsdf extracts, as a binary PLY with a face list; read_points_ply: the positions
+of a point-cloud PLY (the ground truth of adgs.geometry).
 File I/O on the host; nothing here is on the per-frame path.
 """
 import os
@@ -173,6 +174,15 @@ def read_mesh_ply(path, normals=False):
     if vertices is None:
         raise ValueError("%s has no vertex element" % path)
     return (vertices, faces, colors, vnormals) if normals else (vertices, faces, colors)
+
+
+def read_points_ply(path):
+    """The x, y, z of the first element of a PLY file (read_ply: binary or ascii; a LiDAR sweep, a COLMAP cloud, the vertices of a mesh
+    whose faces follow) -> [P, 3] float32 numpy array."""
+    names, cols = read_ply(path)
+    if not all(n in cols for n in "xyz"):
+        raise ValueError("%s: the first element has no x, y, z properties (it has %s)" % (path, names))
+    return np.stack([cols[n] for n in "xyz"], axis=1).astype(np.float32)
 
 
 def save_ply(model, path):
