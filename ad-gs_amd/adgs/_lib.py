@@ -181,6 +181,12 @@ SIGNATURES = {
     "adgs_geometry_sample": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.c_ulonglong, c_p, c_p, c_p]),
     "adgs_geometry_stats_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "adgs_geometry_distance_stats": (c_i, [c_i, c_p, c_i, c_p, ctypes.c_double, c_p, c_p, c_p]),
+    # include/adgs_simplify.h
+    "adgs_simplify_cluster_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_simplify_cluster": (c_i, [c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_simplify_cluster_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_simplify_place_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_simplify_place": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

@@ -4,13 +4,16 @@ volume over the static Gaussians' box, extract the surface by marching tetrahedr
 
     for camera:  render(camera)                         one time stamp per render
                  -> vol.integrate(depth, img_opacity, (camera, pose), image=render, weight=static)
-    vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.mesh.vertex_normals] -> adgs.io.write_mesh_ply
+    vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
+        -> adgs.io.write_mesh_ply
 
     python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json]
-                                    [--keep-largest K] [--min-faces m] [--normals]
+                                    [--keep-largest K] [--min-faces m] [--simplify CELL [--placement quadric|average]] [--normals]
 
 --keep-largest / --min-faces (off by default; either one turns the clean-up on, the other then takes its 2DGS default of 50) drop the small
-connected components of the mesh, --normals writes area-weighted vertex normals into the PLY (adgs.mesh).
+connected components of the mesh, --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
+between the clean-up and the normals (adgs.simplify; below one voxel it only welds), --normals writes area-weighted vertex normals into
+the PLY (adgs.mesh).
 
 Synthetic scene: a cloud of random Gaussians is no surface, so the mesh is a crust around what the cameras saw of it --
 the point here is the loop and its cost.  The cameras advance 0.35 m per view along the viewing direction with a small alternating yaw
@@ -32,9 +35,11 @@ for p in (ROOT, os.path.join(ROOT, "ad-gs_amd"), os.path.join(ROOT, "examples"))
 from multiview_step import neighbour_of  # noqa: E402
 
 
-def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False):
+def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False,
+        simplify=None, placement="quadric"):
     import torch
     from adgs import io, mesh, synthetic, tsdf
+    from adgs import simplify as simplification
     from adgs.model import SyntheticGaussianModel
     from gaussian_renderer import render
     device = device or torch.device("cuda", 0)
@@ -71,6 +76,11 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
         keep = comps.select(largest=K, min_faces=m)
         vertices, faces, colors, _ = mesh.keep_components(comps, keep, vertices, faces, colors=colors)
         cleanup = {"largest": K, "min_faces": m, "components": len(comps), "kept_components": int(keep.sum())}
+    simplified = None
+    if simplify is not None:
+        before = (int(vertices.shape[0]), int(faces.shape[0]))
+        vertices, faces, colors = simplification.simplify_mesh(vertices, faces, colors, cell_size=simplify * voxel, placement=placement)
+        simplified = {"cell_voxels": simplify, "cell_size": simplify * voxel, "placement": placement, "vertices_before": before[0], "faces_before": before[1]}
     vnormals = mesh.vertex_normals(vertices, faces) if normals else None
     torch.cuda.synchronize()
     t3 = time.perf_counter()
@@ -78,7 +88,7 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
     v2, f2, c2, n2 = io.read_mesh_ply(out, normals=True)
     assert v2.shape == tuple(vertices.shape) and f2.shape == tuple(faces.shape) and c2.shape == tuple(colors.shape)
     assert (n2 is None) == (vnormals is None) and (n2 is None or n2.shape == v2.shape)
-    return {"extracted": extracted, "cleanup": cleanup, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras, "dims": list(vol.dims),
+    return {"extracted": extracted, "cleanup": cleanup, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras, "dims": list(vol.dims),
             "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()), "vertices": int(vertices.shape[0]),
             "faces": int(faces.shape[0]), "render_and_integrate_ms": 1e3 * (t1 - t0), "extract_ms": 1e3 * (t2 - t1), "ply": out,
             "ply_bytes": os.path.getsize(out)}
@@ -93,12 +103,15 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep the components with at least as many faces as the K-th largest")
     ap.add_argument("--min-faces", type=int, default=None, metavar="m", help="and with at least m faces")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a lattice of CELL voxels (adgs.simplify)")
+    ap.add_argument("--placement", choices=("quadric", "average"), default="quadric", help="where the vertex of a cluster goes")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
-    res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals)
+    res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals, simplify=a.simplify,
+              placement=a.placement)
     if a.json:
         print(json.dumps(res))
     else:
@@ -107,11 +120,13 @@ def main():
                   res["config"], res["gaussians"], res["cameras"], res["image"][0], res["image"][1], *res["dims"], res["voxel_size"],
                   100 * res["observed_share"], res["vertices"], res["faces"], res["render_and_integrate_ms"], res["extract_ms"], res["ply"],
                   res["ply_bytes"]))
-        if res["cleanup"] or res["normals"]:
+        s = res["simplify"]
+        if res["cleanup"] or res["normals"] or s:
             c = res["cleanup"]
-            print("extracted V %d, F %d%s -> V %d, F %d%s; clean-up and normals %.1f ms" % (
+            print("extracted V %d, F %d%s%s -> V %d, F %d%s; clean-up, simplification and normals %.1f ms" % (
                 res["extracted"]["vertices"], res["extracted"]["faces"],
                 "; %d components, kept %d (largest %d, min_faces %d)" % (c["components"], c["kept_components"], c["largest"], c["min_faces"]) if c else "",
+                "; V %d, F %d simplified at %.2f voxels (%s)" % (s["vertices_before"], s["faces_before"], s["cell_voxels"], s["placement"]) if s else "",
                 res["vertices"], res["faces"], ", with vertex normals" if res["normals"] else "", res["cleanup_and_normals_ms"]))
 
 
