@@ -162,6 +162,15 @@ SIGNATURES = {
     "adgs_tsdf_extract_owner_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "adgs_tsdf_extract_count": (c_i, [c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
     "adgs_tsdf_extract_emit": (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_sparse_tsdf.h
+    "adgs_sparse_tsdf_allocate_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_sparse_tsdf_allocate_view": (c_i, [c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_longlong, c_p, c_p, c_p]),
+    "adgs_sparse_tsdf_allocate_blocks": (c_i, [c_p, c_p, ctypes.c_longlong, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_sparse_tsdf_integrate": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_sparse_tsdf_extract_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_sparse_tsdf_extract_owner_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "adgs_sparse_tsdf_extract_count": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+    "adgs_sparse_tsdf_extract_emit": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_mesh.h
     "adgs_mesh_label_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
     "adgs_mesh_label": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),

@@ -85,6 +85,45 @@ def _positive(x, name, who):
     return v
 
 
+def _view_arguments(who, volume_device, has_color, depth, img_opacity, camera, image, weight, min_opacity, max_depth, near):
+    """The checked arguments of an integrating (or allocating) call -> (H, W, tan, pose12, min_opacity, near, max_depth, depth, opacity,
+    image, weight), the maps detached and contiguous.  Everything is checked before anything is launched."""
+    _check_map(depth, "depth", None, None, None, who)
+    H, W = depth.shape[-2:]
+    _check_map(img_opacity, "img_opacity", H, W, depth.device, who)
+    if isinstance(camera, (tuple, list)) and len(camera) == 2 and torch.is_tensor(camera[1]):
+        tan, pose = _tanfov(camera[0], who), _pose12(camera[1], who)
+    elif hasattr(camera, "world_view_transform"):
+        tan, pose = _tanfov(camera, who), _pose12(camera_pose(camera), who)
+    else:
+        raise TypeError("%s: camera must be (camera or (tanfovx, tanfovy), pose) or a camera with a world_view_transform, got %r" % (who, camera))
+    if (image is None) == has_color:
+        raise ValueError("%s: image must be given exactly when the volume has colour" % who)
+    if image is not None:
+        if not torch.is_tensor(image):
+            raise TypeError("%s: image must be a tensor, got %s" % (who, type(image).__name__))
+        if tuple(image.shape) != (3, H, W):
+            raise ValueError("%s: image must be [3, H, W] = [3, %d, %d], got %s" % (who, H, W, tuple(image.shape)))
+        if image.dtype != torch.float32:
+            raise TypeError("%s: image must be float32, got %s" % (who, image.dtype))
+        if image.device != depth.device:
+            raise RuntimeError("%s: image is on %s, depth on %s" % (who, image.device, depth.device))
+    mo = _min_opacity(min_opacity, who)
+    md, nr = float(max_depth), float(near)
+    if not md > 0.0:
+        raise ValueError("%s: max_depth must be > 0 (inf: no limit), got %r" % (who, max_depth))
+    if not (0.0 <= nr < float("inf")):
+        raise ValueError("%s: near must be finite and >= 0, got %r" % (who, near))
+    w = None if weight is None else _check_weight(weight, H, W, depth.device, who)
+    if not depth.is_cuda:
+        raise RuntimeError("%s: tensors must be on a HIP device; there is no CPU path" % who)
+    if depth.device != volume_device:
+        raise RuntimeError("%s: depth is on %s, the volume on %s" % (who, depth.device, volume_device))
+    d, o = depth.detach().contiguous().reshape(H, W), img_opacity.detach().contiguous().reshape(H, W)
+    img = None if image is None else image.detach().contiguous()
+    return H, W, tan, pose, mo, nr, md, d, o, img, w
+
+
 class TSDFVolume:
     """A dense truncated-signed-distance volume on a HIP device: a lattice of dims = (nx, ny, nz) points, X(i, j, k) = origin +
     voxel_size (i, j, k) in world coordinates, with float32 tensors `tsdf` [nz, ny, nx] (1 = free or unseen), `wsum` [nz, ny, nx]
@@ -166,40 +205,8 @@ class TSDFVolume:
         keeps dynamic objects, the sky and the ego vehicle out of the volume.  A lattice point is updated when it lies beyond `near`
         in front of the camera, its nearest pixel has O >= min_opacity, D > 0 and w > 0, the expected depth z_d there is at most
         max_depth, and it is not more than trunc behind the surface (include/adgs_tsdf.h)."""
-        who = "TSDFVolume.integrate"
-        _check_map(depth, "depth", None, None, None, who)
-        H, W = depth.shape[-2:]
-        _check_map(img_opacity, "img_opacity", H, W, depth.device, who)
-        if isinstance(camera, (tuple, list)) and len(camera) == 2 and torch.is_tensor(camera[1]):
-            tan, pose = _tanfov(camera[0], who), _pose12(camera[1], who)
-        elif hasattr(camera, "world_view_transform"):
-            tan, pose = _tanfov(camera, who), _pose12(camera_pose(camera), who)
-        else:
-            raise TypeError("%s: camera must be (camera or (tanfovx, tanfovy), pose) or a camera with a world_view_transform, got %r" % (who, camera))
-        if (image is None) != (self.color is None):
-            raise ValueError("%s: image must be given exactly when the volume has colour" % who)
-        if image is not None:
-            if not torch.is_tensor(image):
-                raise TypeError("%s: image must be a tensor, got %s" % (who, type(image).__name__))
-            if tuple(image.shape) != (3, H, W):
-                raise ValueError("%s: image must be [3, H, W] = [3, %d, %d], got %s" % (who, H, W, tuple(image.shape)))
-            if image.dtype != torch.float32:
-                raise TypeError("%s: image must be float32, got %s" % (who, image.dtype))
-            if image.device != depth.device:
-                raise RuntimeError("%s: image is on %s, depth on %s" % (who, image.device, depth.device))
-        mo = _min_opacity(min_opacity, who)
-        md, nr = float(max_depth), float(near)
-        if not md > 0.0:
-            raise ValueError("%s: max_depth must be > 0 (inf: no limit), got %r" % (who, max_depth))
-        if not (0.0 <= nr < float("inf")):
-            raise ValueError("%s: near must be finite and >= 0, got %r" % (who, near))
-        w = None if weight is None else _check_weight(weight, H, W, depth.device, who)
-        if not depth.is_cuda:
-            raise RuntimeError("%s: tensors must be on a HIP device; there is no CPU path" % who)
-        if depth.device != self.device:
-            raise RuntimeError("%s: depth is on %s, the volume on %s" % (who, depth.device, self.device))
-        d, o = depth.detach().contiguous().reshape(H, W), img_opacity.detach().contiguous().reshape(H, W)
-        img = None if image is None else image.detach().contiguous()
+        H, W, tan, pose, mo, nr, md, d, o, img, w = _view_arguments("TSDFVolume.integrate", self.device, self.color is not None, depth, img_opacity, camera,
+                                                                    image, weight, min_opacity, max_depth, near)
         if self.tsdf.numel() and d.numel():
             _lib.call("adgs_tsdf_integrate", self.device, ctypes.byref(self._desc()),
                       ctypes.byref(make_view_desc(H, W, inv_depth, tan, mo, nr, md, self.trunc, self.max_weight, pose)), d.data_ptr(), o.data_ptr(),

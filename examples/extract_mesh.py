@@ -7,8 +7,13 @@ volume over the static Gaussians' box, extract the surface by marching tetrahedr
     vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
         -> adgs.io.write_mesh_ply
 
-    python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json]
+    python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json] [--sparse [--margin 2]]
                                     [--keep-largest K] [--min-faces m] [--simplify CELL [--placement quadric|average]] [--normals]
+
+--sparse fuses into a block-sparse volume (adgs.tsdf_sparse) instead of the dense box: no box is chosen, only the 8 x 8 x 8 blocks near the
+rendered surfaces are stored.  It allocates for ALL views first and then integrates them all with allocate=False -- the order that gives
+the dense volume's values (a block allocated by a later view would otherwise miss the free space the earlier views saw) -- so the renders
+are kept between the two loops.  Everything downstream is the same; --json then also reports the blocks and the bytes held.
 
 --keep-largest / --min-faces (off by default; either one turns the clean-up on, the other then takes its 2DGS default of 50) drop the small
 connected components of the mesh, --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
@@ -22,6 +27,7 @@ and a voxel size chosen against the depth noise.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -36,9 +42,9 @@ from multiview_step import neighbour_of  # noqa: E402
 
 
 def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False,
-        simplify=None, placement="quadric"):
+        simplify=None, placement="quadric", sparse=False, margin=2.0):
     import torch
-    from adgs import io, mesh, synthetic, tsdf
+    from adgs import io, mesh, synthetic, tsdf, tsdf_sparse
     from adgs import simplify as simplification
     from adgs.model import SyntheticGaussianModel
     from gaussian_renderer import render
@@ -54,15 +60,24 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
     pipe = types.SimpleNamespace(inv_depth=True, debug=False)
     xyz = model._scene_xyz.detach()                                # the static Gaussians' centres
     voxel = float((xyz.max(0).values - xyz.min(0).values).max()) / resolution
-    vol = tsdf.TSDFVolume.around(xyz, voxel, margin=2 * voxel)
+    extent = (xyz.max(0).values - xyz.min(0).values + 4 * voxel).tolist()      # the box TSDFVolume.around would take, for comparison
+    box_dims = [int(math.ceil(e / voxel)) + 1 for e in extent]
+    vol = tsdf_sparse.SparseTSDFVolume(voxel, margin=margin, device=device) if sparse else tsdf.TSDFVolume.around(xyz, voxel, margin=2 * voxel)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with torch.no_grad():
+        kept = []
         for cam, pose in zip(cams, poses):
             pkg = render(cam, model, None, pipe, render_objmask=True)
             static = (pkg["img_semantic"][0] < 0.5).float()        # zero on the dynamic objects: the volume assumes a static surface
+            if sparse:                                             # first every view's blocks ...
+                vol.allocate(pkg["depth"], pkg["img_opacity"], (cam, pose), weight=static, inv_depth=pipe.inv_depth)
+                kept.append((pkg["depth"], pkg["img_opacity"], pkg["render"].clamp(0, 1).contiguous(), static))
+                continue
             vol.integrate(pkg["depth"], pkg["img_opacity"], (cam, pose), image=pkg["render"].clamp(0, 1).contiguous(), weight=static,
                           inv_depth=pipe.inv_depth)
+        for (depth, opacity, image, static), cam, pose in zip(kept, cams, poses):      # ... then every view into all of them
+            vol.integrate(depth, opacity, (cam, pose), image=image, weight=static, inv_depth=pipe.inv_depth, allocate=False)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     vertices, faces, colors = vol.extract_mesh(min_weight=1.0)
@@ -88,8 +103,10 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
     v2, f2, c2, n2 = io.read_mesh_ply(out, normals=True)
     assert v2.shape == tuple(vertices.shape) and f2.shape == tuple(faces.shape) and c2.shape == tuple(colors.shape)
     assert (n2 is None) == (vnormals is None) and (n2 is None or n2.shape == v2.shape)
-    return {"extracted": extracted, "cleanup": cleanup, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras, "dims": list(vol.dims),
-            "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()), "vertices": int(vertices.shape[0]),
+    return {"extracted": extracted, "cleanup": cleanup, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras,
+            "dims": box_dims if sparse else list(vol.dims), "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()),
+            "sparse": {"blocks": vol.num_blocks, "bytes": int(vol.memory_bytes), "block_bytes": vol.num_blocks * 512 * 20, "margin": margin,
+                       "dense_box_bytes": 20 * box_dims[0] * box_dims[1] * box_dims[2], "skipped_samples": vol.skipped_samples} if sparse else None, "vertices": int(vertices.shape[0]),
             "faces": int(faces.shape[0]), "render_and_integrate_ms": 1e3 * (t1 - t0), "extract_ms": 1e3 * (t2 - t1), "ply": out,
             "ply_bytes": os.path.getsize(out)}
 
@@ -106,12 +123,14 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a lattice of CELL voxels (adgs.simplify)")
     ap.add_argument("--placement", choices=("quadric", "average"), default="quadric", help="where the vertex of a cluster goes")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
+    ap.add_argument("--sparse", action="store_true", help="fuse into a block-sparse volume (adgs.tsdf_sparse): allocate for all views, then integrate them all")
+    ap.add_argument("--margin", type=float, default=2.0, metavar="VOXELS", help="with --sparse: how far around a ray sample blocks are allocated (0 .. 4)")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
     res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals, simplify=a.simplify,
-              placement=a.placement)
+              placement=a.placement, sparse=a.sparse, margin=a.margin)
     if a.json:
         print(json.dumps(res))
     else:
@@ -120,6 +139,10 @@ def main():
                   res["config"], res["gaussians"], res["cameras"], res["image"][0], res["image"][1], *res["dims"], res["voxel_size"],
                   100 * res["observed_share"], res["vertices"], res["faces"], res["render_and_integrate_ms"], res["extract_ms"], res["ply"],
                   res["ply_bytes"]))
+        if res["sparse"]:
+            b = res["sparse"]
+            print("block-sparse volume: %d blocks, %d bytes held (%d in blocks) against %d for the dense box above; the observed share is of the blocks' points"
+                  % (b["blocks"], b["bytes"], b["block_bytes"], b["dense_box_bytes"]))
         s = res["simplify"]
         if res["cleanup"] or res["normals"] or s:
             c = res["cleanup"]
