@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <cmath>
 #include <string>
 
 namespace adgs {
@@ -53,7 +54,18 @@ void set_error(const std::string& msg);
 		if (debug) ADGS_HIP_CHECK(hipStreamSynchronize(stream));                         \
 	} while (0)
 
+// hipLaunchKernelGGL with its arguments, then the check of the launch error.  A macro, so that the __FILE__:__LINE__ of ADGS_HIP_CHECK
+// names the launch and its `return -1` leaves the function that launched.
+#define ADGS_LAUNCH(kernel, grid, block, lds, stream, ...)                               \
+	do {                                                                                 \
+		hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);               \
+		ADGS_HIP_CHECK(hipGetLastError());                                               \
+	} while (0)
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// finite and > 0: what the entry points ask of a size, a distance or a field of view (a float argument converts exactly)
+inline bool positive(double x) { return std::isfinite(x) && x > 0.0; }
 
 // sign(d) as a float, 0 at 0 and at NaN (torch.abs backward); the comparison is made in the argument's type
 __device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
@@ -102,6 +114,20 @@ size_t scan_temp_bytes(size_t n);
 int exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, char* temp, hipStream_t stream);
 constexpr int SCAN_AUX_SLOTS = 32;
 int exclusive_scan_u32_sum(const uint32_t* in, uint32_t* out, size_t n, char* temp, const uint32_t* aux_in, unsigned long long* aux_total, hipStream_t stream);
+// The one read-back of a count pass.  totals (device): ROWS rows of SCAN_AUX_SLOTS partial totals, one row per exclusive_scan_u32_sum, then
+// COUNTERS plain counters.  Copies them, waits for the stream and gives the sum of each row and the counters (NULL without any).
+template <int ROWS, int COUNTERS>
+int read_scan_totals(const unsigned long long* totals, hipStream_t stream, unsigned long long (&sum)[ROWS], unsigned long long* counters) {
+	unsigned long long host[ROWS * SCAN_AUX_SLOTS + COUNTERS];
+	ADGS_HIP_CHECK(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, stream));
+	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
+	for (int r = 0; r < ROWS; r++) {
+		sum[r] = 0;
+		for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
+	}
+	for (int k = 0; k < COUNTERS; k++) counters[k] = host[ROWS * SCAN_AUX_SLOTS + k];
+	return 0;
+}
 
 size_t sort_temp_bytes(size_t n);
 // Stable LSD radix sort of (key,value) pairs on key bits [0, end_bit).

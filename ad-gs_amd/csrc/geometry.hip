@@ -7,14 +7,14 @@
 //   sample   one thread per sample: three splitmix64 words, an upper-bound search of the cdf, one point
 //   stats    one partial row per workgroup over a fixed partition, a one-workgroup finish: no atomics
 #include "common.h"
+#include "mesh_shared.h"
 #include "../../include/adgs_geometry.h"
-#include <climits>
 #include <cmath>
 
 namespace adgs {
 namespace {
 
-constexpr int GEO_THREADS = 256;
+constexpr int GEO_THREADS = MESH_THREADS;                      // blocks_of (mesh_shared.h) counts workgroups of this size
 constexpr int MAX_AXIS_CELLS = 1 << 21;
 constexpr int MAX_RADIUS = 8;
 constexpr int MAX_THRESHOLDS = 4;
@@ -180,20 +180,7 @@ __global__ void __launch_bounds__(GEO_THREADS) geometry_nearest_kernel(const flo
 	idx[qi] = best_index == INT_MAX ? -1 : best_index;
 }
 
-// ---- surface sampling ----
-
-// true and i[] set when the three indices of face f lie in [0, V): checked before every dereference
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, uint32_t f, uint32_t V, uint32_t i[3]) {
-	i[0] = (uint32_t)faces[3 * (size_t)f + 0]; i[1] = (uint32_t)faces[3 * (size_t)f + 1]; i[2] = (uint32_t)faces[3 * (size_t)f + 2];
-	return i[0] < V && i[1] < V && i[2] < V;                    // a negative index is >= 2^31 > V as unsigned
-}
-
-__device__ __forceinline__ void load_corners(const float* __restrict__ vertices, const uint32_t i[3], double p[3][3]) {
-#pragma unroll
-	for (int k = 0; k < 3; k++)
-#pragma unroll
-		for (int d = 0; d < 3; d++) p[k][d] = (double)vertices[3 * (size_t)i[k] + d];
-}
+// ---- surface sampling (load_face, load_corners, face_edges: mesh_shared.h) ----
 
 __global__ void __launch_bounds__(GEO_THREADS) geometry_areas_kernel(const float* __restrict__ vertices, const int* __restrict__ faces, uint32_t V, uint32_t F,
 	double* __restrict__ areas) {
@@ -204,9 +191,8 @@ __global__ void __launch_bounds__(GEO_THREADS) geometry_areas_kernel(const float
 	if (load_face(faces, f, V, i)) {
 		double p[3][3];
 		load_corners(vertices, i, p);
-		const double ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
-		const double bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
-		const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+		const FaceEdges e = face_edges(p[0], p[1], p[2]);
+		const double nx = e.cross_x(), ny = e.cross_y(), nz = e.cross_z();
 		a = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
 	}
 	areas[f] = a;
@@ -324,10 +310,6 @@ __global__ void __launch_bounds__(GEO_THREADS) geometry_stats_finish_kernel(cons
 
 // ---- host ----
 
-unsigned blocks_of(size_t n) { return (unsigned)((n + GEO_THREADS - 1) / GEO_THREADS); }
-bool count_ok(long long n) { return n >= 0 && n <= (long long)INT_MAX; }
-bool positive(double v) { return std::isfinite(v) && v > 0.0; }
-
 // build: the box of the plan, two copies of the keys and values (the sort ping-pongs), the head flags (scanned in place), the scratch of the
 // sort and of the scan (used one after the other)
 struct GridTemp { uint32_t* box; uint64_t *k0, *k1; uint32_t *v0, *v1, *flag; char* prim; size_t bytes; };
@@ -375,8 +357,7 @@ bool grid_of(const std::string& name, float cell_size, const float* origin, cons
 	}
 	g.cell = (double)cell_size;
 	total = (uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2];      // <= 2^63
-	key_bits = 1;                                               // the keys are 0 .. total
-	while (key_bits < 64 && (total >> key_bits) != 0) key_bits++;
+	key_bits = bits_of(total, 64);                              // the keys are 0 .. total
 	return true;
 }
 
@@ -401,8 +382,7 @@ extern "C" int adgs_geometry_grid_plan(int M, const float* points, float cell_si
 	const GridTemp t = carve_grid((char*)temp, (size_t)M);
 	const uint32_t init[8] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u };
 	ADGS_HIP_CHECK(hipMemcpyAsync(t.box, init, sizeof(init), hipMemcpyHostToDevice, stream));
-	hipLaunchKernelGGL(geometry_box_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (uint32_t)M, t.box);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(geometry_box_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (uint32_t)M, t.box);
 	uint32_t host[8];
 	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.box, sizeof(host), hipMemcpyDeviceToHost, stream));
 	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
@@ -435,16 +415,13 @@ extern "C" int adgs_geometry_grid_build(int M, const float* points, float cell_s
 	hipStream_t stream = (hipStream_t)stream_;
 	const GridTemp t = carve_grid((char*)temp, (size_t)M);
 	ADGS_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned int), stream));
-	hipLaunchKernelGGL(geometry_keys_kernel<false>, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (uint32_t)M, g, total, t.k0, t.v0);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(geometry_keys_kernel<false>, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (uint32_t)M, g, total, t.k0, t.v0);
 	if (radix_sort_pairs_u64(t.k0, t.k1, t.v0, t.v1, (size_t)M, bits, t.prim, stream) != 0) return -1;
-	hipLaunchKernelGGL(geometry_gather_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (const uint64_t*)t.k1, (const uint32_t*)t.v1, (uint32_t)M,
+	ADGS_LAUNCH(geometry_gather_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, points, (const uint64_t*)t.k1, (const uint32_t*)t.v1, (uint32_t)M,
 		total, reinterpret_cast<float4*>(records), t.flag);
-	ADGS_HIP_CHECK(hipGetLastError());
 	if (exclusive_scan_u32(t.flag, t.flag, (size_t)M, t.prim, stream) != 0) return -1;
-	hipLaunchKernelGGL(geometry_cells_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, (const uint64_t*)t.k1, (const uint32_t*)t.flag, (uint32_t)M, total,
+	ADGS_LAUNCH(geometry_cells_kernel, dim3(blocks_of(M)), dim3(GEO_THREADS), 0, stream, (const uint64_t*)t.k1, (const uint32_t*)t.flag, (uint32_t)M, total,
 		reinterpret_cast<uint64_t*>(cell_keys), cell_starts, counts);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
 
@@ -471,21 +448,18 @@ extern "C" int adgs_geometry_nearest(int M, int N, const float* queries, float m
 	if (N == 0) return 0;
 	hipStream_t stream = (hipStream_t)stream_;
 	if (empty) {
-		hipLaunchKernelGGL(geometry_fill_kernel, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, (uint32_t)N, dist2, idx);
-		ADGS_HIP_CHECK(hipGetLastError());
+		ADGS_LAUNCH(geometry_fill_kernel, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, (uint32_t)N, dist2, idx);
 		return 0;
 	}
 	const NearestTemp t = carve_nearest((char*)temp, (size_t)N);
 	const double max_dist2 = (double)max_dist * (double)max_dist;
 	float limit = (float)max_dist2;                             // the largest float that passes (double)d2 <= max_dist2 ...
 	if ((double)limit > max_dist2) limit = std::nextafter(limit, 0.0f);      // ... FLT_MAX when max_dist2 is beyond the floats
-	hipLaunchKernelGGL(geometry_keys_kernel<true>, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, queries, (uint32_t)N, g, total, t.k0, t.v0);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(geometry_keys_kernel<true>, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, queries, (uint32_t)N, g, total, t.k0, t.v0);
 	if (radix_sort_pairs_u64(t.k0, t.k1, t.v0, t.v1, (size_t)N, bits, t.sort, stream) != 0) return -1;
-	hipLaunchKernelGGL(geometry_nearest_kernel, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, queries, (const uint32_t*)t.v1, (uint32_t)N, (uint32_t)M, g,
+	ADGS_LAUNCH(geometry_nearest_kernel, dim3(blocks_of(N)), dim3(GEO_THREADS), 0, stream, queries, (const uint32_t*)t.v1, (uint32_t)N, (uint32_t)M, g,
 		(int)cells, limit, reinterpret_cast<const float4*>(records), reinterpret_cast<const uint64_t*>(cell_keys), cell_starts,
 		counts, dist2, idx);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
 
@@ -494,8 +468,7 @@ extern "C" int adgs_geometry_face_areas(int V, int F, const float* vertices, con
 	if (V < 0 || F < 0) { set_error(name + ": negative V or F"); return -1; }
 	if (F > 0 && (!faces || !areas || (V > 0 && !vertices))) { set_error(name + ": NULL pointer"); return -1; }
 	if (F == 0) return 0;
-	hipLaunchKernelGGL(geometry_areas_kernel, dim3(blocks_of(F)), dim3(GEO_THREADS), 0, (hipStream_t)stream_, vertices, faces, (uint32_t)V, (uint32_t)F, areas);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(geometry_areas_kernel, dim3(blocks_of(F)), dim3(GEO_THREADS), 0, (hipStream_t)stream_, vertices, faces, (uint32_t)V, (uint32_t)F, areas);
 	return 0;
 }
 
@@ -507,9 +480,8 @@ extern "C" int adgs_geometry_sample(int V, int F, int n, const float* vertices, 
 	if (F == 0) { set_error(name + ": no face to sample from"); return -1; }
 	if (!positive(total)) { set_error(name + ": the total area (cdf[F - 1]) must be finite and positive"); return -1; }
 	if (!faces || !cdf || !points || !face || (V > 0 && !vertices)) { set_error(name + ": NULL pointer"); return -1; }
-	hipLaunchKernelGGL(geometry_sample_kernel, dim3(blocks_of(n)), dim3(GEO_THREADS), 0, (hipStream_t)stream_, vertices, faces, cdf, (uint32_t)V, (uint32_t)F,
+	ADGS_LAUNCH(geometry_sample_kernel, dim3(blocks_of(n)), dim3(GEO_THREADS), 0, (hipStream_t)stream_, vertices, faces, cdf, (uint32_t)V, (uint32_t)F,
 		(uint32_t)n, total, std::nextafter(total, 0.0), (uint64_t)seed, points, face);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
 
@@ -540,10 +512,8 @@ extern "C" int adgs_geometry_distance_stats(int N, const float* dist2, int num_t
 		const size_t per = (groups + STATS_MAX_BLOCKS - 1) / STATS_MAX_BLOCKS;
 		chunk = (uint32_t)(per * GEO_THREADS);
 		rows = (uint32_t)(((size_t)N + chunk - 1) / chunk);
-		hipLaunchKernelGGL(geometry_stats_kernel, dim3(rows), dim3(GEO_THREADS), 0, stream, dist2, (uint32_t)N, chunk, a, t.sum, t.cnt);
-		ADGS_HIP_CHECK(hipGetLastError());
+		ADGS_LAUNCH(geometry_stats_kernel, dim3(rows), dim3(GEO_THREADS), 0, stream, dist2, (uint32_t)N, chunk, a, t.sum, t.cnt);
 	}
-	hipLaunchKernelGGL(geometry_stats_finish_kernel, dim3(1), dim3(GEO_THREADS), 0, stream, (const double*)t.sum, (const unsigned long long*)t.cnt, rows, (uint32_t)N, out);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(geometry_stats_finish_kernel, dim3(1), dim3(GEO_THREADS), 0, stream, (const double*)t.sum, (const unsigned long long*)t.cnt, rows, (uint32_t)N, out);
 	return 0;
 }

@@ -5,15 +5,14 @@
 //   table    one launch over the vertices (root, vertex counts), one over the faces (face counts, areas): one atomic per run of a component
 //   keep     flags from keep[vertex_component] -> two scans -> one emit launch for the vertex attributes, one for the faces
 //   normals  3 F (vertex, corner) pairs -> stable radix sort by vertex -> one thread per vertex finds its row by bisection and sums it in order
-// Every kernel that reads `faces` checks the three indices against V before it uses them and skips the face otherwise.
+// Every kernel that reads `faces` checks the three indices against V before it uses them (load_face, mesh_shared.h) and skips the face otherwise.
 #include "common.h"
+#include "mesh_shared.h"
 #include "../../include/adgs_mesh.h"
-#include <climits>
 
 namespace adgs {
 namespace {
 
-constexpr int MESH_THREADS = 256;
 constexpr uint32_t NO_COMPONENT = 0xFFFFFFFFu;
 
 // ---- union-find ----
@@ -59,12 +58,6 @@ __device__ __forceinline__ void uf_union(uint32_t* __restrict__ parent, uint32_t
 __global__ void __launch_bounds__(MESH_THREADS) mesh_init_kernel(uint32_t* __restrict__ parent, uint32_t V) {
 	const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
 	if (v < V) parent[v] = v;
-}
-
-// true and i[] set when the three indices of face f lie in [0, V)
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, uint32_t f, uint32_t V, uint32_t i[3]) {
-	i[0] = (uint32_t)faces[3 * (size_t)f + 0]; i[1] = (uint32_t)faces[3 * (size_t)f + 1]; i[2] = (uint32_t)faces[3 * (size_t)f + 2];
-	return i[0] < V && i[1] < V && i[2] < V;                    // a negative index is >= 2^31 > V as unsigned
 }
 
 __global__ void __launch_bounds__(MESH_THREADS) mesh_link_kernel(const int* __restrict__ faces, uint32_t F, uint32_t V, uint32_t* __restrict__ parent,
@@ -187,13 +180,9 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_table_faces_kernel(const in
 				c = cv;
 				if (AREA) {
 					double p[3][3];
-#pragma unroll
-					for (int k = 0; k < 3; k++)
-#pragma unroll
-						for (int d = 0; d < 3; d++) p[k][d] = (double)vertices[3 * (size_t)i[k] + d];
-					const double ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
-					const double bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
-					const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+					load_corners(vertices, i, p);
+					const FaceEdges e = face_edges(p[0], p[1], p[2]);
+					const double nx = e.cross_x(), ny = e.cross_y(), nz = e.cross_z();
 					a = 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
 				}
 			}
@@ -272,25 +261,16 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_normals_kernel(const float*
 	const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
 	if (v >= V) return;
 	const size_t n = 3 * (size_t)F;
-	size_t lo = 0, hi = n;                                      // the first position with keys[] >= v: at most 34 steps
-	while (lo < hi) {
-		const size_t mid = lo + (hi - lo) / 2;
-		if (keys[mid] < v) lo = mid + 1; else hi = mid;
-	}
 	double sx = 0.0, sy = 0.0, sz = 0.0, S = 0.0;
-	for (size_t j = lo; j < n && keys[j] == v; j++) {
+	for (size_t j = first_at_least(keys, n, v); j < n && keys[j] == v; j++) {
 		const uint32_t f = vals[j] / 3u;
 		uint32_t i[3];
 		if (f >= F || !load_face(faces, f, V, i)) continue;
 		double p[3][3];
-#pragma unroll
-		for (int k = 0; k < 3; k++)
-#pragma unroll
-			for (int d = 0; d < 3; d++) p[k][d] = (double)vertices[3 * (size_t)i[k] + d];
-		const double ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
-		const double bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
-		sx += ay * bz - az * by; sy += az * bx - ax * bz; sz += ax * by - ay * bx;
-		S += sqrt(ax * ax + ay * ay + az * az) * sqrt(bx * bx + by * by + bz * bz);
+		load_corners(vertices, i, p);
+		const FaceEdges e = face_edges(p[0], p[1], p[2]);
+		sx += e.cross_x(); sy += e.cross_y(); sz += e.cross_z();
+		S += sqrt(e.ax * e.ax + e.ay * e.ay + e.az * e.az) * sqrt(e.bx * e.bx + e.by * e.by + e.bz * e.bz);
 	}
 	const double len = sqrt(sx * sx + sy * sy + sz * sz);
 	const bool zero = !(S > 0.0) || !(len > 0x1p-40 * S);
@@ -301,7 +281,6 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_normals_kernel(const float*
 
 // ---- host ----
 
-unsigned blocks_of(size_t n) { return (unsigned)((n + MESH_THREADS - 1) / MESH_THREADS); }
 unsigned table_blocks_of(size_t n) { return (unsigned)((n + TABLE_ITEMS - 1) / TABLE_ITEMS); }
 
 // label: the parent array, the counters (the scan's SCAN_AUX_SLOTS partial totals of C, then the bad-face count), the scan's scratch
@@ -328,18 +307,7 @@ KeepTemp carve_keep(char* base, size_t V, size_t F) {
 	return t;
 }
 
-struct NormalsTemp { uint32_t *k0, *k1, *v0, *v1; char* sort; size_t bytes; };
-NormalsTemp carve_normals(char* base, size_t F) {
-	Carver c(base);
-	NormalsTemp t;
-	const size_t n = 3 * F;
-	t.k0 = c.take<uint32_t>(n); t.k1 = c.take<uint32_t>(n); t.v0 = c.take<uint32_t>(n); t.v1 = c.take<uint32_t>(n);
-	t.sort = c.take<char>(sort_temp_bytes(n));
-	t.bytes = c.size();
-	return t;
-}
-
-bool sizes_ok(long long V, long long F) { return V >= 0 && F >= 0 && V <= (long long)INT_MAX && F <= (long long)INT_MAX; }
+// normals: the (vertex, corner) pairs and their sort, CornerPairTemp of mesh_shared.h
 
 } // namespace
 } // namespace adgs
@@ -365,26 +333,17 @@ extern "C" int adgs_mesh_label(int V, int F, const int* faces, void* temp, int* 
 		unsigned long long* bad = t.totals + SCAN_AUX_SLOTS;
 		uint32_t* comp = reinterpret_cast<uint32_t*>(vertex_component);
 		ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 2 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
-		hipLaunchKernelGGL(mesh_init_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, t.parent, (uint32_t)V);
-		ADGS_HIP_CHECK(hipGetLastError());
-		if (F > 0) {
-			hipLaunchKernelGGL(mesh_link_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (uint32_t)F, (uint32_t)V, t.parent, bad);
-			ADGS_HIP_CHECK(hipGetLastError());
-		}
-		hipLaunchKernelGGL(mesh_flatten_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, t.parent, (uint32_t)V, comp);
-		ADGS_HIP_CHECK(hipGetLastError());
+		ADGS_LAUNCH(mesh_init_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, t.parent, (uint32_t)V);
+		if (F > 0) ADGS_LAUNCH(mesh_link_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (uint32_t)F, (uint32_t)V, t.parent, bad);
+		ADGS_LAUNCH(mesh_flatten_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, t.parent, (uint32_t)V, comp);
 		if (exclusive_scan_u32_sum(comp, comp, (size_t)V, t.scan, comp, t.totals, stream) != 0) return -1;
-		hipLaunchKernelGGL(mesh_component_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.parent, (uint32_t)V, comp);
-		ADGS_HIP_CHECK(hipGetLastError());
-		unsigned long long host[SCAN_AUX_SLOTS + 1];
-		ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
-		ADGS_HIP_CHECK(hipStreamSynchronize(stream));
-		unsigned long long C = 0;
-		for (int s = 0; s < SCAN_AUX_SLOTS; s++) C += host[s];
-		if (C > (unsigned long long)V || host[SCAN_AUX_SLOTS] > (unsigned long long)F) {      // cannot happen: bounded by V and F < 2^31
+		ADGS_LAUNCH(mesh_component_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.parent, (uint32_t)V, comp);
+		unsigned long long C[1], nbad;
+		if (read_scan_totals<1, 1>(t.totals, stream, C, &nbad) != 0) return -1;
+		if (C[0] > (unsigned long long)V || nbad > (unsigned long long)F) {      // cannot happen: bounded by V and F < 2^31
 			set_error(name + ": a count exceeds INT_MAX"); return -1;
 		}
-		counts[0] = (long long)C; counts[1] = (long long)host[SCAN_AUX_SLOTS];
+		counts[0] = (long long)C[0]; counts[1] = (long long)nbad;
 	}
 	if (counts[1] > 0) {
 		set_error(name + ": " + std::to_string(counts[1]) + " faces index outside the " + std::to_string(V) + " vertices");
@@ -408,15 +367,13 @@ extern "C" int adgs_mesh_table(int V, int F, int C, const int* faces, const floa
 	ADGS_HIP_CHECK(hipMemsetAsync(num_faces, 0, (size_t)C * sizeof(int), stream));
 	ADGS_HIP_CHECK(hipMemsetAsync(num_vertices, 0, (size_t)C * sizeof(int), stream));
 	if (area) ADGS_HIP_CHECK(hipMemsetAsync(area, 0, (size_t)C * sizeof(double), stream));
-	hipLaunchKernelGGL(mesh_table_vertices_kernel, dim3(table_blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.parent, vertex_component, (uint32_t)V,
+	ADGS_LAUNCH(mesh_table_vertices_kernel, dim3(table_blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.parent, vertex_component, (uint32_t)V,
 		(uint32_t)C, root, num_vertices);
-	ADGS_HIP_CHECK(hipGetLastError());
 	if (F > 0) {
-		if (area) hipLaunchKernelGGL(mesh_table_faces_kernel<true>, dim3(table_blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, vertices, vertex_component,
+		if (area) ADGS_LAUNCH(mesh_table_faces_kernel<true>, dim3(table_blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, vertices, vertex_component,
 			(uint32_t)F, (uint32_t)V, (uint32_t)C, num_faces, area);
-		else hipLaunchKernelGGL(mesh_table_faces_kernel<false>, dim3(table_blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, vertices, vertex_component,
+		else ADGS_LAUNCH(mesh_table_faces_kernel<false>, dim3(table_blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, vertices, vertex_component,
 			(uint32_t)F, (uint32_t)V, (uint32_t)C, num_faces, area);
-		ADGS_HIP_CHECK(hipGetLastError());
 	}
 	return 0;
 }
@@ -437,17 +394,12 @@ extern "C" int adgs_mesh_keep_count(int V, int F, int C, const int* faces, const
 	hipStream_t stream = (hipStream_t)stream_;
 	const KeepTemp t = carve_keep((char*)temp, (size_t)V, (size_t)F);
 	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 2 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
-	hipLaunchKernelGGL(mesh_keep_flags_kernel, dim3(blocks_of((size_t)(V > F ? V : F))), dim3(MESH_THREADS), 0, stream, faces, vertex_component, keep,
+	ADGS_LAUNCH(mesh_keep_flags_kernel, dim3(blocks_of((size_t)(V > F ? V : F))), dim3(MESH_THREADS), 0, stream, faces, vertex_component, keep,
 		(uint32_t)V, (uint32_t)F, (uint32_t)C, t.vmap, t.fmap);
-	ADGS_HIP_CHECK(hipGetLastError());
 	if (exclusive_scan_u32_sum(t.vmap, t.vmap, (size_t)V, t.scan, t.vmap, t.totals, stream) != 0) return -1;
 	if (F > 0 && exclusive_scan_u32_sum(t.fmap, t.fmap, (size_t)F, t.scan, t.fmap, t.totals + SCAN_AUX_SLOTS, stream) != 0) return -1;
-	unsigned long long host[2 * SCAN_AUX_SLOTS];
-	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
-	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
-	unsigned long long sum[2] = { 0, 0 };
-	for (int r = 0; r < 2; r++)
-		for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
+	unsigned long long sum[2];
+	if (read_scan_totals<2, 0>(t.totals, stream, sum, nullptr) != 0) return -1;
 	if (sum[0] > (unsigned long long)V || sum[1] > (unsigned long long)F) { set_error(name + ": a count exceeds INT_MAX"); return -1; }     // cannot happen
 	counts[0] = (long long)sum[0]; counts[1] = (long long)sum[1];
 	return 0;
@@ -467,19 +419,15 @@ extern "C" int adgs_mesh_keep_emit(int V, int F, const int* faces, const float* 
 	if (V2 == 0) return 0;                                      // no vertex stays, hence no face
 	hipStream_t stream = (hipStream_t)stream_;
 	const KeepTemp t = carve_keep((char*)temp, (size_t)V, (size_t)F);
-	hipLaunchKernelGGL(mesh_keep_vertices_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.vmap, (uint32_t)V, (uint32_t)V2, vertices,
+	ADGS_LAUNCH(mesh_keep_vertices_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, (const uint32_t*)t.vmap, (uint32_t)V, (uint32_t)V2, vertices,
 		colors, normals, vertices_out, colors_out, normals_out);
-	ADGS_HIP_CHECK(hipGetLastError());
-	if (F2 > 0) {
-		hipLaunchKernelGGL(mesh_keep_faces_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (const uint32_t*)t.vmap, (const uint32_t*)t.fmap,
-			(uint32_t)V, (uint32_t)F, (uint32_t)V2, (uint32_t)F2, faces_out);
-		ADGS_HIP_CHECK(hipGetLastError());
-	}
+	if (F2 > 0) ADGS_LAUNCH(mesh_keep_faces_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (const uint32_t*)t.vmap, (const uint32_t*)t.fmap,
+		(uint32_t)V, (uint32_t)F, (uint32_t)V2, (uint32_t)F2, faces_out);
 	return 0;
 }
 
 extern "C" size_t adgs_mesh_normals_temp_bytes(long long V, long long F) {
-	return sizes_ok(V, F) ? carve_normals(nullptr, (size_t)F).bytes : 0;
+	return sizes_ok(V, F) ? carve_corner_pairs(nullptr, (size_t)F).bytes : 0;
 }
 
 extern "C" int adgs_mesh_vertex_normals(int V, int F, const float* vertices, const int* faces, void* temp, float* normals, void* stream_) {
@@ -488,17 +436,13 @@ extern "C" int adgs_mesh_vertex_normals(int V, int F, const float* vertices, con
 	if ((V > 0 && (!vertices || !normals)) || (F > 0 && (!faces || !temp))) { set_error(name + ": NULL pointer"); return -1; }
 	if (V == 0) return 0;
 	hipStream_t stream = (hipStream_t)stream_;
-	const NormalsTemp t = carve_normals((char*)temp, (size_t)F);
+	const CornerPairTemp t = carve_corner_pairs((char*)temp, (size_t)F);
 	const uint32_t* keys = t.k1;
 	const uint32_t* vals = t.v1;
 	if (F > 0) {
-		hipLaunchKernelGGL(mesh_corner_pairs_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (uint32_t)F, (uint32_t)V, t.k0, t.v0);
-		ADGS_HIP_CHECK(hipGetLastError());
-		int bits = 1;                                           // the keys are 0 .. V
-		while (bits < 32 && ((unsigned long long)V >> bits) != 0) bits++;
-		if (radix_sort_pairs_u32(t.k0, t.k1, t.v0, t.v1, 3 * (size_t)F, bits, t.sort, stream) != 0) return -1;
+		ADGS_LAUNCH(mesh_corner_pairs_kernel, dim3(blocks_of(F)), dim3(MESH_THREADS), 0, stream, faces, (uint32_t)F, (uint32_t)V, t.k0, t.v0);
+		if (radix_sort_pairs_u32(t.k0, t.k1, t.v0, t.v1, 3 * (size_t)F, bits_of((unsigned long long)V), t.sort, stream) != 0) return -1;      // the keys are 0 .. V
 	}
-	hipLaunchKernelGGL(mesh_normals_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, vertices, faces, keys, vals, (uint32_t)V, (uint32_t)F, normals);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(mesh_normals_kernel, dim3(blocks_of(V)), dim3(MESH_THREADS), 0, stream, vertices, faces, keys, vals, (uint32_t)V, (uint32_t)F, normals);
 	return 0;
 }

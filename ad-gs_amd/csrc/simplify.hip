@@ -5,17 +5,17 @@
 //            order -> keep flags -> used roots flagged over the vertices -> three scans (vertices, member counts, faces) -> ONE read-back
 //   emit     roots, member CSR, renumbered faces from the scans
 //   place    3 F (cluster, corner) pairs -> stable sort by cluster -> one thread per cluster sums its members and its corner row in order
-// Every kernel that reads `faces` checks the three indices against V before it uses them.  Counters are integer atomics (one per wave);
-// there is no float atomic, and a flag written by several lanes is a plain store of the same value.
+// Every kernel that reads `faces` checks the three indices against V before it uses them (load_face, mesh_shared.h).  Counters are integer
+// atomics (one per wave); there is no float atomic, and a flag written by several lanes is a plain store of the same value.
 #include "common.h"
+#include "mesh_shared.h"
 #include "../../include/adgs_simplify.h"
-#include <climits>
 #include <cmath>
 
 namespace adgs {
 namespace {
 
-constexpr int SIMP_THREADS = 256;
+constexpr int SIMP_THREADS = MESH_THREADS;                     // blocks_of (mesh_shared.h) counts workgroups of this size
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr double AXIS_LIMIT = 1048576.0;                       // 2^20: |c| below it is keyed in 21 bits per axis
 constexpr int KEY_BITS = 63;
@@ -23,7 +23,7 @@ constexpr int KEY_BITS = 63;
 enum { CNT_NONFINITE = 0, CNT_UNKEYED, CNT_BAD, CNT_DROPPED, CNT_DEGENERATE, CNT_DUPLICATE, CNT_COUNT };
 constexpr int TOTALS = 3 * SCAN_AUX_SLOTS + CNT_COUNT;
 
-struct Lattice { double origin[3]; double cell; };
+struct CellLattice { double origin[3]; double cell; };
 
 // adds the number of lanes of the wave with `p` to *counter: one atomic per wave that has any
 __device__ __forceinline__ void count_lanes(bool p, unsigned long long* __restrict__ counter) {
@@ -31,15 +31,9 @@ __device__ __forceinline__ void count_lanes(bool p, unsigned long long* __restri
 	if (m && (int)(threadIdx.x & (WAVE - 1)) == __ffsll((long long)m) - 1) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
-// true and i[] set when the three indices of face f lie in [0, V)
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, uint32_t f, uint32_t V, uint32_t i[3]) {
-	i[0] = (uint32_t)faces[3 * (size_t)f + 0]; i[1] = (uint32_t)faces[3 * (size_t)f + 1]; i[2] = (uint32_t)faces[3 * (size_t)f + 2];
-	return i[0] < V && i[1] < V && i[2] < V;                    // a negative index is >= 2^31 > V as unsigned
-}
-
 // ---- clusters ----
 
-__global__ void __launch_bounds__(SIMP_THREADS) simplify_keys_kernel(const float* __restrict__ vertices, uint32_t V, Lattice g, uint64_t* __restrict__ keys,
+__global__ void __launch_bounds__(SIMP_THREADS) simplify_keys_kernel(const float* __restrict__ vertices, uint32_t V, CellLattice g, uint64_t* __restrict__ keys,
 	uint32_t* __restrict__ vals, unsigned long long* __restrict__ counters) {
 	const uint32_t v = blockIdx.x * (uint32_t)SIMP_THREADS + threadIdx.x;
 	bool nonfinite = false, unkeyed = false;
@@ -236,11 +230,6 @@ __global__ void __launch_bounds__(SIMP_THREADS) simplify_emit_faces_kernel(const
 
 // ---- placement ----
 
-__device__ __forceinline__ void load_point(const float* __restrict__ a, uint32_t v, double p[3]) {
-#pragma unroll
-	for (int d = 0; d < 3; d++) p[d] = (double)a[3 * (size_t)v + d];
-}
-
 __device__ __forceinline__ bool finite3(const double p[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
 // the (cluster, corner id) pairs; the key V2 is for a corner that no cluster sums
@@ -270,7 +259,7 @@ __global__ void __launch_bounds__(SIMP_THREADS) simplify_corner_pairs_kernel(con
 template <bool QUADRIC>
 __global__ void __launch_bounds__(SIMP_THREADS) simplify_place_kernel(const float* __restrict__ vertices, const int* __restrict__ faces,
 	const float* __restrict__ colors, const int* __restrict__ member_starts, const int* __restrict__ members, const uint32_t* __restrict__ keys,
-	const uint32_t* __restrict__ vals, uint32_t V, uint32_t F, uint32_t V2, uint32_t M, Lattice g, double lambda, float* __restrict__ vertices_out,
+	const uint32_t* __restrict__ vals, uint32_t V, uint32_t F, uint32_t V2, uint32_t M, CellLattice g, double lambda, float* __restrict__ vertices_out,
 	float* __restrict__ colors_out) {
 	const uint32_t d = blockIdx.x * (uint32_t)SIMP_THREADS + threadIdx.x;
 	if (d >= V2) return;
@@ -294,22 +283,16 @@ __global__ void __launch_bounds__(SIMP_THREADS) simplify_place_kernel(const floa
 	double delta[3] = { 0.0, 0.0, 0.0 };
 	if (QUADRIC && count) {
 		const size_t len = 3 * (size_t)F;
-		size_t lo = 0, hi = len;                                    // the first position with keys[] >= d: at most 34 steps
-		while (lo < hi) {
-			const size_t mid = lo + (hi - lo) / 2;
-			if (keys[mid] < d) lo = mid + 1; else hi = mid;
-		}
 		double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, t = 0.0;
-		for (size_t j = lo; j < len && keys[j] == d; j++) {
+		for (size_t j = first_at_least(keys, len, d); j < len && keys[j] == d; j++) {
 			const uint32_t f = vals[j] / 3u, k = vals[j] % 3u;
 			uint32_t i[3];
 			if (f >= F || !load_face(faces, f, V, i)) continue;
 			double p[3][3];
 #pragma unroll
-			for (int c = 0; c < 3; c++) load_point(vertices, i[c], p[c]);
-			const double ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
-			const double bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
-			const double kx = ay * bz - az * by, ky = az * bx - ax * bz, kz = ax * by - ay * bx;
+			for (int c = 0; c < 3; c++) load_point(vertices, i[c], p[c]);      // as load_corners does; through it the compiler emits other (equal-valued) code here
+			const FaceEdges e = face_edges(p[0], p[1], p[2]);
+			const double kx = e.cross_x(), ky = e.cross_y(), kz = e.cross_z();
 			const double L = sqrt(kx * kx + ky * ky + kz * kz);
 			if (!(L > 0.0)) continue;
 			const double nx = kx / L, ny = ky / L, nz = kz / L, w = L / 2.0;
@@ -348,8 +331,6 @@ __global__ void __launch_bounds__(SIMP_THREADS) simplify_place_kernel(const floa
 
 // ---- host ----
 
-unsigned blocks_of(size_t n) { return (unsigned)((n + SIMP_THREADS - 1) / SIMP_THREADS); }
-
 // cluster: the sort's ping-pong buffers (the 64-bit keys serve the vertices, then the faces), the maps that emit reads, the totals (three
 // rows of SCAN_AUX_SLOTS partial totals: V2, M, F2; then the counters), the sort's and the scan's scratch (one user at a time)
 struct ClusterTemp {
@@ -373,26 +354,9 @@ ClusterTemp carve_cluster(char* base, size_t V, size_t F) {
 	return t;
 }
 
-struct PlaceTemp { uint32_t *k0, *k1, *v0, *v1; char* sort; size_t bytes; };
-PlaceTemp carve_place(char* base, size_t F) {
-	Carver c(base);
-	PlaceTemp t;
-	const size_t n = 3 * F;
-	t.k0 = c.take<uint32_t>(n); t.k1 = c.take<uint32_t>(n); t.v0 = c.take<uint32_t>(n); t.v1 = c.take<uint32_t>(n);
-	t.sort = c.take<char>(sort_temp_bytes(n));
-	t.bytes = c.size();
-	return t;
-}
+// place: the (cluster, corner) pairs and their sort, CornerPairTemp of mesh_shared.h
 
-bool sizes_ok(long long V, long long F) { return V >= 0 && F >= 0 && V <= (long long)INT_MAX && F <= (long long)INT_MAX; }
-
-int bits_of(unsigned long long top) {                           // the keys are 0 .. top
-	int bits = 1;
-	while (bits < 32 && (top >> bits) != 0) bits++;
-	return bits;
-}
-
-bool lattice_of(float cell_size, const float* origin, Lattice& g) {
+bool lattice_of(float cell_size, const float* origin, CellLattice& g) {
 	if (!origin || !(cell_size > 0.f) || !std::isfinite(cell_size)) return false;
 	for (int k = 0; k < 3; k++) {
 		if (!std::isfinite(origin[k])) return false;
@@ -416,7 +380,7 @@ extern "C" int adgs_simplify_cluster(int V, int F, const float* vertices, const 
 	const std::string name("adgs_simplify_cluster");
 	if (V < 0 || F < 0) { set_error(name + ": negative V or F"); return -1; }
 	if (!counts) { set_error(name + ": NULL counts"); return -1; }
-	Lattice g;
+	CellLattice g;
 	if (!lattice_of(cell_size, origin, g)) { set_error(name + ": cell_size must be a positive finite number and origin three finite floats"); return -1; }
 	if ((F > 0 && !faces) || (V > 0 && (!vertices || !temp || !vertex_cluster))) { set_error(name + ": NULL pointer"); return -1; }
 	for (int k = 0; k < 9; k++) counts[k] = 0;
@@ -430,52 +394,39 @@ extern "C" int adgs_simplify_cluster(int V, int F, const float* vertices, const 
 		const uint32_t uV = (uint32_t)V, uF = (uint32_t)F;
 		ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, TOTALS * sizeof(unsigned long long), stream));
 		ADGS_HIP_CHECK(hipMemsetAsync(t.used, 0, (size_t)V * sizeof(uint32_t), stream));
-		hipLaunchKernelGGL(simplify_keys_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, vertices, uV, g, t.k0, t.sv0, counters);
-		ADGS_HIP_CHECK(hipGetLastError());
+		ADGS_LAUNCH(simplify_keys_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, vertices, uV, g, t.k0, t.sv0, counters);
 		if (radix_sort_pairs_u64(t.k0, t.k1, t.sv0, t.sv, (size_t)V, KEY_BITS, t.sort, stream) != 0) return -1;
-		hipLaunchKernelGGL(simplify_heads_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint64_t*)t.k1, uV, t.head);
-		ADGS_HIP_CHECK(hipGetLastError());
+		ADGS_LAUNCH(simplify_heads_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint64_t*)t.k1, uV, t.head);
 		if (exclusive_scan_u32(t.head, t.head, (size_t)V, t.scan, stream) != 0) return -1;
-		hipLaunchKernelGGL(simplify_assign_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint64_t*)t.k1, (const uint32_t*)t.sv,
+		ADGS_LAUNCH(simplify_assign_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint64_t*)t.k1, (const uint32_t*)t.sv,
 			(const uint32_t*)t.head, uV, t.kc, t.cstart);
-		ADGS_HIP_CHECK(hipGetLastError());
 		if (F > 0) {
-			hipLaunchKernelGGL(simplify_face_third_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, uF, uV, t.fa0, t.fb0,
+			ADGS_LAUNCH(simplify_face_third_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, uF, uV, t.fa0, t.fb0,
 				counters);
-			ADGS_HIP_CHECK(hipGetLastError());
 			const int vbits = bits_of((unsigned long long)V);
 			if (radix_sort_pairs_u32(t.fa0, t.fa1, t.fb0, t.fb1, (size_t)F, vbits, t.sort, stream) != 0) return -1;
-			hipLaunchKernelGGL(simplify_face_pair_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint32_t*)t.fb1,
+			ADGS_LAUNCH(simplify_face_pair_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint32_t*)t.fb1,
 				uF, uV, t.k0);
-			ADGS_HIP_CHECK(hipGetLastError());
 			if (radix_sort_pairs_u64(t.k0, t.k1, t.fb1, t.fb0, (size_t)F, 32 + vbits, t.sort, stream) != 0) return -1;
-			hipLaunchKernelGGL(simplify_face_keep_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint64_t*)t.k1,
+			ADGS_LAUNCH(simplify_face_keep_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint64_t*)t.k1,
 				(const uint32_t*)t.fb0, uF, uV, t.fkeep, counters);
-			ADGS_HIP_CHECK(hipGetLastError());
-			hipLaunchKernelGGL(simplify_used_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint32_t*)t.fkeep,
+			ADGS_LAUNCH(simplify_used_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, (const uint32_t*)t.kc, (const uint32_t*)t.fkeep,
 				(const uint32_t*)t.sv, (const uint32_t*)t.cstart, uF, uV, t.used);
-			ADGS_HIP_CHECK(hipGetLastError());
 		}
-		hipLaunchKernelGGL(simplify_sizes_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.kc, (const uint32_t*)t.used,
+		ADGS_LAUNCH(simplify_sizes_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.kc, (const uint32_t*)t.used,
 			(const uint32_t*)t.cstart, uV, t.mscan);
-		ADGS_HIP_CHECK(hipGetLastError());
 		if (exclusive_scan_u32_sum(t.used, t.vmap, (size_t)V, t.scan, t.used, t.totals, stream) != 0) return -1;
 		if (exclusive_scan_u32_sum(t.mscan, t.mscan, (size_t)V, t.scan, t.mscan, t.totals + SCAN_AUX_SLOTS, stream) != 0) return -1;
 		if (F > 0 && exclusive_scan_u32_sum(t.fkeep, t.fmap, (size_t)F, t.scan, t.fkeep, t.totals + 2 * SCAN_AUX_SLOTS, stream) != 0) return -1;
-		hipLaunchKernelGGL(simplify_vertex_cluster_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.kc, (const uint32_t*)t.used,
+		ADGS_LAUNCH(simplify_vertex_cluster_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.kc, (const uint32_t*)t.used,
 			(const uint32_t*)t.vmap, (const uint32_t*)t.sv, (const uint32_t*)t.cstart, uV, vertex_cluster);
-		ADGS_HIP_CHECK(hipGetLastError());
-		unsigned long long host[TOTALS];
-		ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
-		ADGS_HIP_CHECK(hipStreamSynchronize(stream));
-		unsigned long long sum[3] = { 0, 0, 0 };
-		for (int r = 0; r < 3; r++)
-			for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
+		unsigned long long sum[3], cnt[CNT_COUNT];
+		if (read_scan_totals<3, CNT_COUNT>(t.totals, stream, sum, cnt) != 0) return -1;
 		bool fits = sum[0] <= (unsigned long long)V && sum[1] <= (unsigned long long)V && sum[2] <= (unsigned long long)F && sum[0] <= sum[1];
-		for (int k = 0; k < CNT_COUNT; k++) fits = fits && host[3 * SCAN_AUX_SLOTS + k] <= (unsigned long long)(k < CNT_BAD ? V : F);
+		for (int k = 0; k < CNT_COUNT; k++) fits = fits && cnt[k] <= (unsigned long long)(k < CNT_BAD ? V : F);
 		if (!fits) { set_error(name + ": a count exceeds its bound"); return -1; }     // cannot happen: bounded by V and F < 2^31
 		counts[0] = (long long)sum[0]; counts[1] = (long long)sum[2]; counts[2] = (long long)sum[1];
-		for (int k = 0; k < CNT_COUNT; k++) counts[3 + k] = (long long)host[3 * SCAN_AUX_SLOTS + k];
+		for (int k = 0; k < CNT_COUNT; k++) counts[3 + k] = (long long)cnt[k];
 	}
 	if (counts[5] > 0) {
 		set_error(name + ": " + std::to_string(counts[5]) + " faces index outside the " + std::to_string(V) + " vertices");
@@ -502,20 +453,16 @@ extern "C" int adgs_simplify_cluster_emit(int V, int F, const int* faces, const 
 	if (V == 0) return 0;
 	hipStream_t stream = (hipStream_t)stream_;
 	const ClusterTemp t = carve_cluster((char*)temp, (size_t)V, (size_t)F);
-	hipLaunchKernelGGL(simplify_emit_vertices_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.sv, (const uint32_t*)t.kc,
+	ADGS_LAUNCH(simplify_emit_vertices_kernel, dim3(blocks_of(V)), dim3(SIMP_THREADS), 0, stream, (const uint32_t*)t.sv, (const uint32_t*)t.kc,
 		(const uint32_t*)t.cstart, (const uint32_t*)t.used, (const uint32_t*)t.vmap, (const uint32_t*)t.mscan, (uint32_t)V, (uint32_t)V2, (uint32_t)M, root,
 		num_vertices, member_starts, members);
-	ADGS_HIP_CHECK(hipGetLastError());
-	if (F2 > 0) {
-		hipLaunchKernelGGL(simplify_emit_faces_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, vertex_cluster, (const uint32_t*)t.fkeep,
-			(const uint32_t*)t.fmap, (uint32_t)F, (uint32_t)V, (uint32_t)F2, faces_out, face_source);
-		ADGS_HIP_CHECK(hipGetLastError());
-	}
+	if (F2 > 0) ADGS_LAUNCH(simplify_emit_faces_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, faces, vertex_cluster, (const uint32_t*)t.fkeep,
+		(const uint32_t*)t.fmap, (uint32_t)F, (uint32_t)V, (uint32_t)F2, faces_out, face_source);
 	return 0;
 }
 
 extern "C" size_t adgs_simplify_place_temp_bytes(long long V, long long F) {
-	return sizes_ok(V, F) ? carve_place(nullptr, (size_t)F).bytes : 0;
+	return sizes_ok(V, F) ? carve_corner_pairs(nullptr, (size_t)F).bytes : 0;
 }
 
 extern "C" int adgs_simplify_place(int V, int F, int V2, int M, const float* vertices, const int* faces, const float* colors, const int* vertex_cluster,
@@ -527,7 +474,7 @@ extern "C" int adgs_simplify_place(int V, int F, int V2, int M, const float* ver
 	if (3ull * (unsigned long long)F > 0xFFFFFFFFull) { set_error(name + ": 3 F must be below 2^32"); return -1; }
 	if (placement != 0 && placement != 1) { set_error(name + ": placement must be 0 (average) or 1 (quadric)"); return -1; }
 	if (!(regularization > 0.0) || !std::isfinite(regularization)) { set_error(name + ": regularization must be a positive finite number"); return -1; }
-	Lattice g;
+	CellLattice g;
 	if (!lattice_of(cell_size, origin, g)) { set_error(name + ": cell_size must be a positive finite number and origin three finite floats"); return -1; }
 	if ((colors != nullptr) != (colors_out != nullptr)) { set_error(name + ": colors and colors_out must be given together"); return -1; }
 	if (V2 > 0 && (!vertices || !vertex_cluster || !member_starts || !members || !vertices_out || (F > 0 && (!faces || !temp)))) {
@@ -535,20 +482,18 @@ extern "C" int adgs_simplify_place(int V, int F, int V2, int M, const float* ver
 	}
 	if (V2 == 0) return 0;
 	hipStream_t stream = (hipStream_t)stream_;
-	const PlaceTemp t = carve_place((char*)temp, (size_t)F);
+	const CornerPairTemp t = carve_corner_pairs((char*)temp, (size_t)F);
 	const bool quadric = placement == 1 && F > 0;               // without a face there is no quadric: delta = 0
 	if (quadric) {
-		hipLaunchKernelGGL(simplify_corner_pairs_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, vertices, faces, vertex_cluster, (uint32_t)F,
+		ADGS_LAUNCH(simplify_corner_pairs_kernel, dim3(blocks_of(F)), dim3(SIMP_THREADS), 0, stream, vertices, faces, vertex_cluster, (uint32_t)F,
 			(uint32_t)V, (uint32_t)V2, t.k0, t.v0);
-		ADGS_HIP_CHECK(hipGetLastError());
 		if (radix_sort_pairs_u32(t.k0, t.k1, t.v0, t.v1, 3 * (size_t)F, bits_of((unsigned long long)V2), t.sort, stream) != 0) return -1;
-		hipLaunchKernelGGL(simplify_place_kernel<true>, dim3(blocks_of(V2)), dim3(SIMP_THREADS), 0, stream, vertices, faces, colors, member_starts, members,
+		ADGS_LAUNCH(simplify_place_kernel<true>, dim3(blocks_of(V2)), dim3(SIMP_THREADS), 0, stream, vertices, faces, colors, member_starts, members,
 			(const uint32_t*)t.k1, (const uint32_t*)t.v1, (uint32_t)V, (uint32_t)F, (uint32_t)V2, (uint32_t)M, g, regularization, vertices_out, colors_out);
 	} else {
-		hipLaunchKernelGGL(simplify_place_kernel<false>, dim3(blocks_of(V2)), dim3(SIMP_THREADS), 0, stream, vertices, faces, colors, member_starts, members,
+		ADGS_LAUNCH(simplify_place_kernel<false>, dim3(blocks_of(V2)), dim3(SIMP_THREADS), 0, stream, vertices, faces, colors, member_starts, members,
 			(const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)V, (uint32_t)F, (uint32_t)V2, (uint32_t)M, g, regularization, vertices_out,
 			colors_out);
 	}
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }

@@ -51,24 +51,6 @@ __device__ __forceinline__ void split_index(const Lattice& L, unsigned idx, int&
 	i = (int)(idx - row * (unsigned)L.nx); k = (int)(row / (unsigned)L.ny); j = (int)(row - (unsigned)k * (unsigned)L.ny);
 }
 
-// exclusive prefix of v over the 256 threads of the workgroup, in thread order; total: the sum.  Every thread calls it.
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave /* [5] */, uint32_t& total) {
-	const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-	uint32_t incl = v;
-#pragma unroll
-	for (int off = 1; off < WAVE; off <<= 1) {
-		const uint32_t o = __shfl_up(incl, off, WAVE);
-		if (lane >= off) incl += o;
-	}
-	__syncthreads();                                            // a previous use of s_wave is over
-	if (lane == WAVE - 1) s_wave[wid] = incl;
-	__syncthreads();
-	uint32_t before = 0; total = 0;
-#pragma unroll
-	for (int w = 0; w < TSDF_THREADS / WAVE; w++) { const uint32_t t = s_wave[w]; if (w < wid) before += t; total += t; }
-	return before + incl - v;
-}
-
 // EMIT false: the three counts of the chunk.  EMIT true: the chunk's vertices and, when it has any, its owner words.
 template <bool EMIT>
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_points_kernel(Lattice L, const float* __restrict__ tsdf, const float* __restrict__ wsum,
@@ -80,9 +62,9 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_points_kernel(Lattice L, co
 	int i = 0, j = 0, k = 0;
 	if (idx < L.n) { split_index(L, idx, i, j, k); pc = classify(L, tsdf, wsum, min_weight, idx, i, j, k); }
 	uint32_t nv_chunk, nf_chunk;
-	const uint32_t local = block_exclusive((uint32_t)__popc(pc.vmask), s_wave, nv_chunk);
+	const uint32_t local = block_exclusive<TSDF_THREADS>((uint32_t)__popc(pc.vmask), s_wave, nv_chunk);
 	if (!EMIT) {
-		block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
+		block_exclusive<TSDF_THREADS>(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
 		if (threadIdx.x == 0) { cv[chunk] = nv_chunk; cf[chunk] = nf_chunk; ce[chunk] = nv_chunk ? 1u : 0u; }
 		return;
 	}
@@ -121,7 +103,7 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(Lattice L, con
 	PointClass pc; pc.in8 = 0; pc.vmask = 0; pc.cell = false;
 	if (idx < L.n) { int i, j, k; split_index(L, idx, i, j, k); pc = classify(L, tsdf, wsum, min_weight, idx, i, j, k); }
 	uint32_t nf_chunk;
-	const uint32_t local = block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
+	const uint32_t local = block_exclusive<TSDF_THREADS>(pc.cell ? cell_faces(pc.in8) : 0u, s_wave, nf_chunk);
 	if (!pc.cell) return;
 	const unsigned sy = (unsigned)L.nx, sz = (unsigned)L.nx * (unsigned)L.ny;
 	// the vertex on the edge between corners lo < hi (corner bits, lo a subset of hi) of this cell: it exists, so its owner's chunk has an owner word
@@ -134,8 +116,6 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(Lattice L, con
 	cell_emit_faces(pc.in8, vid, (size_t)cf[chunk] + local, n_faces, faces);
 }
 
-bool tsdf_positive(float x) { return std::isfinite(x) && x > 0.f; }
-
 // 0: `L` is set; 1: an empty lattice; -1: refused
 int check_volume(const std::string& name, const adgs_tsdf_volume* vol, Lattice& L) {
 	if (vol->struct_bytes < (int)sizeof(adgs_tsdf_volume)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_volume"); return -1; }
@@ -144,7 +124,7 @@ int check_volume(const std::string& name, const adgs_tsdf_volume* vol, Lattice& 
 	if (xy > (unsigned long long)INT_MAX || xy * (unsigned long long)vol->nz > (unsigned long long)INT_MAX) {
 		set_error(name + ": nx * ny * nz must be below 2^31"); return -1;
 	}
-	if (!tsdf_positive(vol->voxel_size)) { set_error(name + ": voxel_size must be finite and > 0"); return -1; }
+	if (!positive(vol->voxel_size)) { set_error(name + ": voxel_size must be finite and > 0"); return -1; }
 	for (int a = 0; a < 3; a++)
 		if (!std::isfinite(vol->origin[a])) { set_error(name + ": the origin must be finite"); return -1; }
 	L.nx = vol->nx; L.ny = vol->ny; L.nz = vol->nz;
@@ -154,19 +134,8 @@ int check_volume(const std::string& name, const adgs_tsdf_volume* vol, Lattice& 
 	return L.n == 0 ? 1 : 0;
 }
 
+// the rows of the extraction's scratch (ExtractTemp, tsdf_shared.h)
 unsigned chunks_of(const Lattice& L) { return (L.n + (unsigned)TSDF_THREADS - 1u) / (unsigned)TSDF_THREADS; }
-
-// the scratch of the extraction: three uint32 per chunk (vertices, faces, has-vertices; scanned in place), the 64-bit totals, the scan's own scratch
-struct ExtractTemp { uint32_t *cv, *cf, *ce; unsigned long long* totals; char* scan; size_t bytes; };
-ExtractTemp carve_temp(char* base, size_t chunks) {
-	Carver c(base);
-	ExtractTemp t;
-	t.cv = c.take<uint32_t>(chunks); t.cf = c.take<uint32_t>(chunks); t.ce = c.take<uint32_t>(chunks);
-	t.totals = c.take<unsigned long long>(3 * SCAN_AUX_SLOTS);
-	t.scan = c.take<char>(scan_temp_bytes(chunks));
-	t.bytes = c.size();
-	return t;
-}
 
 } // namespace
 } // namespace adgs
@@ -180,36 +149,19 @@ extern "C" int adgs_tsdf_integrate(const adgs_tsdf_volume* vol, const adgs_tsdf_
 	Lattice L;
 	const int c = check_volume(name, vol, L);
 	if (c < 0) return -1;
-	if (view->struct_bytes < (int)sizeof(adgs_tsdf_view)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_view"); return -1; }
-	if (view->H < 0 || view->W < 0) { set_error(name + ": negative H or W"); return -1; }
-	if ((long long)view->H * view->W > (long long)INT_MAX) { set_error(name + ": H * W exceeds INT_MAX"); return -1; }
-	if (!tsdf_positive(view->tanfovx) || !tsdf_positive(view->tanfovy)) { set_error(name + ": tanfovx and tanfovy must be finite and > 0"); return -1; }
-	if (!tsdf_positive(view->trunc)) { set_error(name + ": trunc must be finite and > 0"); return -1; }
-	if (!(tsdf_positive(view->min_opacity) && view->min_opacity <= 1.f)) { set_error(name + ": min_opacity must lie in (0, 1]"); return -1; }
-	if (!(view->max_weight > 0.f)) { set_error(name + ": max_weight must be > 0"); return -1; }
-	if (!(std::isfinite(view->near) && view->near >= 0.f)) { set_error(name + ": near must be finite and >= 0"); return -1; }
-	for (int i = 0; i < 12; i++)
-		if (!std::isfinite(view->pose[i])) { set_error(name + ": the pose must be finite"); return -1; }
+	TsdfView v;
+	if (check_view(name, view, v) < 0) return -1;
 	if ((image != nullptr) != (color != nullptr)) { set_error(name + ": image and color must be given together"); return -1; }
 	if (c == 1 || view->H == 0 || view->W == 0) return 0;
-	TsdfView v;
-	v.H = view->H; v.W = view->W; v.inv_depth = view->inv_depth ? 1 : 0;
-	v.kx = (double)view->W / (2.0 * (double)view->tanfovx); v.ky = (double)view->H / (2.0 * (double)view->tanfovy);
-	v.cx = 0.5 * (double)(view->W - 1); v.cy = 0.5 * (double)(view->H - 1);
-	for (int i = 0; i < 9; i++) v.R[i] = view->pose[i];
-	for (int i = 0; i < 3; i++) v.t[i] = view->pose[9 + i];
-	v.near = (double)view->near; v.max_depth = (double)view->max_depth; v.trunc = (double)view->trunc; v.max_weight = (double)view->max_weight;
-	v.min_opacity = view->min_opacity;
-	hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(chunks_of(L)), dim3(TSDF_THREADS), 0, (hipStream_t)stream_, L, v, depth, opacity, image, weight, tsdf,
+	ADGS_LAUNCH(tsdf_integrate_kernel, dim3(chunks_of(L)), dim3(TSDF_THREADS), 0, (hipStream_t)stream_, L, v, depth, opacity, image, weight, tsdf,
 		wsum, color);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
 
 extern "C" size_t adgs_tsdf_extract_temp_bytes(const adgs_tsdf_volume* vol) {
 	Lattice L;
 	if (!vol || check_volume("adgs_tsdf_extract_temp_bytes", vol, L) < 0) return 0;
-	return carve_temp(nullptr, chunks_of(L)).bytes;
+	return carve_extract(nullptr, chunks_of(L)).bytes;
 }
 
 extern "C" size_t adgs_tsdf_extract_owner_bytes(long long nonempty_chunks) {
@@ -227,26 +179,10 @@ extern "C" int adgs_tsdf_extract_count(const adgs_tsdf_volume* vol, const float*
 	if (c == 1 || L.nx < 2 || L.ny < 2 || L.nz < 2) return 0;     // no cell, hence no vertex and no face
 	hipStream_t stream = (hipStream_t)stream_;
 	const unsigned chunks = chunks_of(L);
-	const ExtractTemp t = carve_temp((char*)temp, chunks);
-	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 3 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
-	hipLaunchKernelGGL(tsdf_points_kernel<false>, dim3(chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, (const float*)nullptr, min_weight, t.cv, t.cf,
+	const ExtractTemp t = carve_extract((char*)temp, chunks);
+	ADGS_LAUNCH(tsdf_points_kernel<false>, dim3(chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, (const float*)nullptr, min_weight, t.cv, t.cf,
 		t.ce, (uint32_t*)nullptr, 0u, (size_t)0, (float*)nullptr, (float*)nullptr);
-	ADGS_HIP_CHECK(hipGetLastError());
-	uint32_t* rows[3] = { t.cv, t.cf, t.ce };
-	for (int r = 0; r < 3; r++)
-		if (exclusive_scan_u32_sum(rows[r], rows[r], chunks, t.scan, rows[r], t.totals + r * SCAN_AUX_SLOTS, stream) != 0) return -1;
-	unsigned long long host[3 * SCAN_AUX_SLOTS];
-	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
-	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
-	unsigned long long sum[3] = { 0, 0, 0 };
-	for (int r = 0; r < 3; r++)
-		for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
-	if (sum[0] > (unsigned long long)INT_MAX || sum[1] > (unsigned long long)INT_MAX) {
-		set_error(name + ": the mesh has " + std::to_string(sum[0]) + " vertices and " + std::to_string(sum[1]) + " faces; more than INT_MAX of either is refused");
-		return -1;
-	}
-	for (int r = 0; r < 3; r++) counts[r] = (long long)sum[r];
-	return 0;
+	return extract_count_tail(name, t, chunks, stream, counts);
 }
 
 extern "C" int adgs_tsdf_extract_emit(const adgs_tsdf_volume* vol, const float* tsdf, const float* wsum, const float* color, float min_weight,
@@ -258,21 +194,13 @@ extern "C" int adgs_tsdf_extract_emit(const adgs_tsdf_volume* vol, const float* 
 	if (c < 0) return -1;
 	const long long V = counts[0], F = counts[1], E = counts[2];
 	const long long chunks = c == 1 ? 0 : (long long)chunks_of(L);
-	if (V < 0 || F < 0 || E < 0 || V > (long long)INT_MAX || F > (long long)INT_MAX || E > chunks || E > V) {
-		set_error(name + ": counts are not what adgs_tsdf_extract_count returned for this volume"); return -1;
-	}
-	if ((V > 0 && !vertices) || (F > 0 && !faces) || (E > 0 && !owners)) { set_error(name + ": NULL vertices, faces or owners"); return -1; }
-	if ((color != nullptr) != (colors != nullptr)) { set_error(name + ": color and colors must be given together"); return -1; }
+	if (check_emit(name, "adgs_tsdf_extract_count", counts, INT_MAX, INT_MAX, chunks, vertices, faces, owners, color, colors) < 0) return -1;
 	if (V == 0 || E == 0) return 0;                              // no vertex, hence no face
 	hipStream_t stream = (hipStream_t)stream_;
-	const ExtractTemp t = carve_temp((char*)temp, (size_t)chunks);
-	hipLaunchKernelGGL(tsdf_points_kernel<true>, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, color, min_weight, t.cv, t.cf, t.ce,
+	const ExtractTemp t = carve_extract((char*)temp, (size_t)chunks);
+	ADGS_LAUNCH(tsdf_points_kernel<true>, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, color, min_weight, t.cv, t.cf, t.ce,
 		(uint32_t*)owners, (unsigned)E, (size_t)V, vertices, colors);
-	ADGS_HIP_CHECK(hipGetLastError());
-	if (F > 0) {
-		hipLaunchKernelGGL(tsdf_faces_kernel, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, min_weight, (const uint32_t*)t.cv,
-			(const uint32_t*)t.cf, (const uint32_t*)t.ce, (const uint32_t*)owners, (unsigned)E, (size_t)F, faces);
-		ADGS_HIP_CHECK(hipGetLastError());
-	}
+	if (F > 0) ADGS_LAUNCH(tsdf_faces_kernel, dim3((unsigned)chunks), dim3(TSDF_THREADS), 0, stream, L, tsdf, wsum, min_weight, (const uint32_t*)t.cv,
+		(const uint32_t*)t.cf, (const uint32_t*)t.ce, (const uint32_t*)owners, (unsigned)E, (size_t)F, faces);
 	return 0;
 }

@@ -1,9 +1,12 @@
 // The device functions that the dense volume (tsdf.hip) and the block-sparse one (tsdf_sparse.hip) share: the per-point update chain of
 // include/adgs_tsdf.h (steps 1-9) and the marching-tetrahedra pieces (the tables, classify, cell_faces, the faces of a cell).  Both files
 // are built with the same flags and call the SAME functions, so a lattice point that both volumes hold and that saw the same views has
-// the same bits in both.
+// the same bits in both.  The host code the two volumes' entry points share is here as well: the check of a view, the scratch of the extraction,
+// the tail of extract_count and the argument checks of extract_emit, each with the entry's name for its messages.
 #pragma once
 #include "common.h"
+#include "../../include/adgs_tsdf.h"
+#include <climits>
 
 namespace adgs {
 namespace {
@@ -21,6 +24,28 @@ struct TsdfView {
 	double near, max_depth, trunc, max_weight;
 	float min_opacity;
 };
+
+// What both volumes refuse of a view, in this order; then `v` is set.  -> 0 or -1
+int check_view(const std::string& name, const adgs_tsdf_view* view, TsdfView& v) {
+	if (view->struct_bytes < (int)sizeof(adgs_tsdf_view)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_view"); return -1; }
+	if (view->H < 0 || view->W < 0) { set_error(name + ": negative H or W"); return -1; }
+	if ((long long)view->H * view->W > (long long)INT_MAX) { set_error(name + ": H * W exceeds INT_MAX"); return -1; }
+	if (!positive(view->tanfovx) || !positive(view->tanfovy)) { set_error(name + ": tanfovx and tanfovy must be finite and > 0"); return -1; }
+	if (!positive(view->trunc)) { set_error(name + ": trunc must be finite and > 0"); return -1; }
+	if (!(positive(view->min_opacity) && view->min_opacity <= 1.f)) { set_error(name + ": min_opacity must lie in (0, 1]"); return -1; }
+	if (!(view->max_weight > 0.f)) { set_error(name + ": max_weight must be > 0"); return -1; }
+	if (!(std::isfinite(view->near) && view->near >= 0.f)) { set_error(name + ": near must be finite and >= 0"); return -1; }
+	for (int i = 0; i < 12; i++)
+		if (!std::isfinite(view->pose[i])) { set_error(name + ": the pose must be finite"); return -1; }
+	v.H = view->H; v.W = view->W; v.inv_depth = view->inv_depth ? 1 : 0;
+	v.kx = (double)view->W / (2.0 * (double)view->tanfovx); v.ky = (double)view->H / (2.0 * (double)view->tanfovy);
+	v.cx = 0.5 * (double)(view->W - 1); v.cy = 0.5 * (double)(view->H - 1);
+	for (int i = 0; i < 9; i++) v.R[i] = view->pose[i];
+	for (int i = 0; i < 3; i++) v.t[i] = view->pose[9 + i];
+	v.near = (double)view->near; v.max_depth = (double)view->max_depth; v.trunc = (double)view->trunc; v.max_weight = (double)view->max_weight;
+	v.min_opacity = view->min_opacity;
+	return 0;
+}
 
 // Steps 1-9 for the lattice point (i, j, k) of the lattice at `L.o` with spacing `L.vs`; t, w: its tsdf and wsum; c: its first colour value (or
 // NULL), the next channel `cstride` floats further.  A point that fails a gate returns before it reads or writes its values.
@@ -179,6 +204,70 @@ __device__ __forceinline__ void cell_emit_faces(uint32_t in8, Vid vid, size_t f,
 			else put(e(a, r2), e(a, r1), e(a, r0));
 		}
 	}
+}
+
+// exclusive prefix of v over the THREADS threads of the workgroup, in thread order; total: the sum.  Every thread calls it.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave /* [THREADS / WAVE] */, uint32_t& total) {
+	const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+	uint32_t incl = v;
+#pragma unroll
+	for (int off = 1; off < WAVE; off <<= 1) {
+		const uint32_t o = __shfl_up(incl, off, WAVE);
+		if (lane >= off) incl += o;
+	}
+	__syncthreads();                                            // a previous use of s_wave is over
+	if (lane == WAVE - 1) s_wave[wid] = incl;
+	__syncthreads();
+	uint32_t before = 0; total = 0;
+#pragma unroll
+	for (int w = 0; w < THREADS / WAVE; w++) { const uint32_t t = s_wave[w]; if (w < wid) before += t; total += t; }
+	return before + incl - v;
+}
+
+// ---- extraction, host ----
+
+// the scratch of the extraction: three uint32 per row (a chunk of the dense volume, a block of the sparse one: vertices, faces, has-vertices;
+// scanned in place), the 64-bit totals, the scan's own scratch
+struct ExtractTemp { uint32_t *cv, *cf, *ce; unsigned long long* totals; char* scan; size_t bytes; };
+ExtractTemp carve_extract(char* base, size_t rows) {
+	Carver c(base);
+	ExtractTemp t;
+	t.cv = c.take<uint32_t>(rows); t.cf = c.take<uint32_t>(rows); t.ce = c.take<uint32_t>(rows);
+	t.totals = c.take<unsigned long long>(3 * SCAN_AUX_SLOTS);
+	t.scan = c.take<char>(scan_temp_bytes(rows));
+	t.bytes = c.size();
+	return t;
+}
+
+// extract_count behind its count kernel, which wrote the three counts of every row: scans them in place, reads the totals back once, refuses a
+// mesh beyond INT_MAX and writes `counts`.  -> 0 or -1
+int extract_count_tail(const std::string& name, const ExtractTemp& t, size_t rows, hipStream_t stream, long long* counts) {
+	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 3 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
+	uint32_t* row[3] = { t.cv, t.cf, t.ce };
+	for (int r = 0; r < 3; r++)
+		if (exclusive_scan_u32_sum(row[r], row[r], rows, t.scan, row[r], t.totals + r * SCAN_AUX_SLOTS, stream) != 0) return -1;
+	unsigned long long sum[3];
+	if (read_scan_totals<3, 0>(t.totals, stream, sum, nullptr) != 0) return -1;
+	if (sum[0] > (unsigned long long)INT_MAX || sum[1] > (unsigned long long)INT_MAX) {
+		set_error(name + ": the mesh has " + std::to_string(sum[0]) + " vertices and " + std::to_string(sum[1]) + " faces; more than INT_MAX of either is refused");
+		return -1;
+	}
+	for (int r = 0; r < 3; r++) counts[r] = (long long)sum[r];
+	return 0;
+}
+
+// What extract_emit refuses of `counts` and of its outputs.  max_V, max_F, max_E: what the volume can hold at most (beside INT_MAX vertices and
+// faces, and an owner row per vertex at most); count_entry: the entry that returned the counts, for the message.  -> 0 or -1
+int check_emit(const std::string& name, const char* count_entry, const long long* counts, long long max_V, long long max_F, long long max_E,
+	const float* vertices, const int* faces, const void* owners, const float* color, const float* colors) {
+	const long long V = counts[0], F = counts[1], E = counts[2];
+	if (V < 0 || F < 0 || E < 0 || V > (long long)INT_MAX || F > (long long)INT_MAX || E > max_E || E > V || V > max_V || F > max_F) {
+		set_error(name + ": counts are not what " + count_entry + " returned for this volume"); return -1;
+	}
+	if ((V > 0 && !vertices) || (F > 0 && !faces) || (E > 0 && !owners)) { set_error(name + ": NULL vertices, faces or owners"); return -1; }
+	if ((color != nullptr) != (colors != nullptr)) { set_error(name + ": color and colors must be given together"); return -1; }
+	return 0;
 }
 
 } // namespace

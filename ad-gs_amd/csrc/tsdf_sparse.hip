@@ -287,24 +287,6 @@ __device__ __forceinline__ Lattice stage_lattice() {
 	return L;
 }
 
-// exclusive prefix of v over the 512 threads of the workgroup, in thread order; total: the sum.  Every thread calls it.
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave, uint32_t& total) {
-	const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-	uint32_t incl = v;
-#pragma unroll
-	for (int off = 1; off < WAVE; off <<= 1) {
-		const uint32_t o = __shfl_up(incl, off, WAVE);
-		if (lane >= off) incl += o;
-	}
-	__syncthreads();                                            // a previous use of s_wave is over
-	if (lane == WAVE - 1) s_wave[wid] = incl;
-	__syncthreads();
-	uint32_t before = 0; total = 0;
-#pragma unroll
-	for (int w = 0; w < EXTRACT_THREADS / WAVE; w++) { const uint32_t t = s_wave[w]; if (w < wid) before += t; total += t; }
-	return before + incl - v;
-}
-
 // the block index (0, 1, 2) -> (-1, 0, +1) of a staged coordinate -1 .. 8
 __device__ __forceinline__ int side(int c) { return c < 0 ? 0 : (c >= SB ? 2 : 1); }
 
@@ -322,9 +304,9 @@ __global__ void __launch_bounds__(EXTRACT_THREADS) sparse_points_kernel(Lattice 
 	const unsigned at = (unsigned)(((lz + 1) * SN + ly + 1) * SN + lx + 1);
 	const PointClass pc = classify(stage_lattice(), S.t, S.w, min_weight, at, lx + 1, ly + 1, lz + 1);
 	uint32_t nv_block, nf_block;
-	const uint32_t local = block_exclusive((uint32_t)__popc(pc.vmask), S.wave, nv_block);
+	const uint32_t local = block_exclusive<EXTRACT_THREADS>((uint32_t)__popc(pc.vmask), S.wave, nv_block);
 	if (!EMIT) {
-		block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, S.wave, nf_block);
+		block_exclusive<EXTRACT_THREADS>(pc.cell ? cell_faces(pc.in8) : 0u, S.wave, nf_block);
 		if (threadIdx.x == 0) { cv[r] = nv_block; cf[r] = nf_block; ce[r] = nv_block ? 1u : 0u; }
 		return;
 	}
@@ -370,7 +352,7 @@ __global__ void __launch_bounds__(EXTRACT_THREADS) sparse_faces_kernel(const uin
 	const unsigned at = (unsigned)(((lz + 1) * SN + ly + 1) * SN + lx + 1);
 	const PointClass pc = classify(stage_lattice(), S.t, S.w, min_weight, at, lx + 1, ly + 1, lz + 1);
 	uint32_t nf_block;
-	const uint32_t local = block_exclusive(pc.cell ? cell_faces(pc.in8) : 0u, S.wave, nf_block);
+	const uint32_t local = block_exclusive<EXTRACT_THREADS>(pc.cell ? cell_faces(pc.in8) : 0u, S.wave, nf_block);
 	if (!pc.cell) return;
 	// the vertex on the edge between corners lo < hi (corner bits, lo a subset of hi) of this cell: it exists, so its owner's block is allocated
 	// and has an owner word
@@ -386,8 +368,6 @@ __global__ void __launch_bounds__(EXTRACT_THREADS) sparse_faces_kernel(const uin
 }
 
 // ---- host ----
-
-bool positive(float x) { return std::isfinite(x) && x > 0.f; }
 
 // 0: fine; -1: refused.  with_pool: num_blocks <= capacity is required
 int check_volume(const std::string& name, const adgs_sparse_tsdf_volume* vol, bool with_pool, Lattice& L) {
@@ -406,28 +386,12 @@ int check_volume(const std::string& name, const adgs_sparse_tsdf_volume* vol, bo
 	return 0;
 }
 
-// what adgs_tsdf_integrate refuses of a view, and trunc / voxel_size above the limit; steps: n
-int check_view(const std::string& name, const adgs_tsdf_view* view, const Lattice& L, TsdfView& v, int& steps) {
-	if (view->struct_bytes < (int)sizeof(adgs_tsdf_view)) { set_error(name + ": struct_bytes is smaller than adgs_tsdf_view"); return -1; }
-	if (view->H < 0 || view->W < 0) { set_error(name + ": negative H or W"); return -1; }
-	if ((long long)view->H * view->W > (long long)INT_MAX) { set_error(name + ": H * W exceeds INT_MAX"); return -1; }
-	if (!positive(view->tanfovx) || !positive(view->tanfovy)) { set_error(name + ": tanfovx and tanfovy must be finite and > 0"); return -1; }
-	if (!positive(view->trunc)) { set_error(name + ": trunc must be finite and > 0"); return -1; }
-	if (!(positive(view->min_opacity) && view->min_opacity <= 1.f)) { set_error(name + ": min_opacity must lie in (0, 1]"); return -1; }
-	if (!(view->max_weight > 0.f)) { set_error(name + ": max_weight must be > 0"); return -1; }
-	if (!(std::isfinite(view->near) && view->near >= 0.f)) { set_error(name + ": near must be finite and >= 0"); return -1; }
-	for (int i = 0; i < 12; i++)
-		if (!std::isfinite(view->pose[i])) { set_error(name + ": the pose must be finite"); return -1; }
+// the shared check of a view (check_view, tsdf_shared.h), then trunc / voxel_size above the limit; steps: n
+int check_view_steps(const std::string& name, const adgs_tsdf_view* view, const Lattice& L, TsdfView& v, int& steps) {
+	if (check_view(name, view, v) < 0) return -1;
 	const double n = std::ceil((double)view->trunc / L.vs);
 	if (!(n <= (double)ADGS_SPARSE_TSDF_MAX_STEPS)) { set_error(name + ": trunc / voxel_size exceeds ADGS_SPARSE_TSDF_MAX_STEPS"); return -1; }
 	steps = n < 1.0 ? 1 : (int)n;
-	v.H = view->H; v.W = view->W; v.inv_depth = view->inv_depth ? 1 : 0;
-	v.kx = (double)view->W / (2.0 * (double)view->tanfovx); v.ky = (double)view->H / (2.0 * (double)view->tanfovy);
-	v.cx = 0.5 * (double)(view->W - 1); v.cy = 0.5 * (double)(view->H - 1);
-	for (int i = 0; i < 9; i++) v.R[i] = view->pose[i];
-	for (int i = 0; i < 3; i++) v.t[i] = view->pose[9 + i];
-	v.near = (double)view->near; v.max_depth = (double)view->max_depth; v.trunc = (double)view->trunc; v.max_weight = (double)view->max_weight;
-	v.min_opacity = view->min_opacity;
 	return 0;
 }
 
@@ -459,16 +423,13 @@ int allocate_tail(const std::string& name, const AllocTemp& t, uint32_t cand_cap
 	uint64_t* keys_out, int* slots_out, int* block_coords, long long* counts, hipStream_t stream) {
 	const uint32_t NB = (uint32_t)vol->num_blocks, room = (uint32_t)vol->table_capacity;
 	if (radix_sort_pairs_u64_dn(t.cand, t.sorted, t.flags, t.pos, cand_cap, &t.state->n_sort, 64, t.sort, stream) != 0) return -1;
-	hipLaunchKernelGGL(sparse_head_flags_kernel, dim3(blocks_for(cand_cap, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, (const uint64_t*)t.sorted, cand_cap, keys, NB,
+	ADGS_LAUNCH(sparse_head_flags_kernel, dim3(blocks_for(cand_cap, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, (const uint64_t*)t.sorted, cand_cap, keys, NB,
 		(const AllocState*)t.state, t.flags);
-	ADGS_HIP_CHECK(hipGetLastError());
 	if (exclusive_scan_u32_sum(t.flags, t.pos, cand_cap, t.scan, t.flags, t.aux + SCAN_AUX_SLOTS, stream) != 0) return -1;
-	hipLaunchKernelGGL(sparse_new_total_kernel, dim3(1), dim3(1), 0, stream, (const unsigned long long*)(t.aux + SCAN_AUX_SLOTS), cand_cap, NB, room, t.state);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(sparse_new_total_kernel, dim3(1), dim3(1), 0, stream, (const unsigned long long*)(t.aux + SCAN_AUX_SLOTS), cand_cap, NB, room, t.state);
 	const size_t n = NB > cand_cap ? NB : cand_cap;
-	hipLaunchKernelGGL(sparse_merge_kernel, dim3(blocks_for(n, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, (const uint64_t*)t.sorted, (const uint32_t*)t.flags,
+	ADGS_LAUNCH(sparse_merge_kernel, dim3(blocks_for(n, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, (const uint64_t*)t.sorted, (const uint32_t*)t.flags,
 		(const uint32_t*)t.pos, keys, slots, NB, room, (const AllocState*)t.state, keys_out, slots_out, block_coords);
-	ADGS_HIP_CHECK(hipGetLastError());
 	unsigned long long host[4];
 	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.state->counts, sizeof(host), hipMemcpyDeviceToHost, stream));
 	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
@@ -479,17 +440,7 @@ int allocate_tail(const std::string& name, const AllocTemp& t, uint32_t cand_cap
 // NULL tables are fine for an empty volume only
 bool table_missing(const adgs_sparse_tsdf_volume* vol, const uint64_t* keys, const int* slots) { return vol->num_blocks > 0 && (!keys || !slots); }
 
-// the scratch of the extraction: three uint32 per block (vertices, faces, has-vertices; scanned in place), the 64-bit totals, the scan's own scratch
-struct ExtractTemp { uint32_t *cv, *cf, *ce; unsigned long long* totals; char* scan; size_t bytes; };
-ExtractTemp carve_extract(char* base, size_t blocks) {
-	Carver c(base);
-	ExtractTemp t;
-	t.cv = c.take<uint32_t>(blocks); t.cf = c.take<uint32_t>(blocks); t.ce = c.take<uint32_t>(blocks);
-	t.totals = c.take<unsigned long long>(3 * SCAN_AUX_SLOTS);
-	t.scan = c.take<char>(scan_temp_bytes(blocks));
-	t.bytes = c.size();
-	return t;
-}
+// the scratch of the extraction: ExtractTemp of tsdf_shared.h, one row per block
 
 } // namespace
 } // namespace adgs
@@ -511,7 +462,7 @@ extern "C" int adgs_sparse_tsdf_allocate_view(const adgs_sparse_tsdf_volume* vol
 	if (table_missing(vol, keys, slots)) { set_error(name + ": NULL pointer"); return -1; }
 	TsdfView tv;
 	int steps;
-	if (check_view(name, view, L, tv, steps) < 0) return -1;
+	if (check_view_steps(name, view, L, tv, steps) < 0) return -1;
 	if (!(margin >= 0.f && margin <= 4.f)) { set_error(name + ": margin must lie in [0, 4]"); return -1; }
 	if (max_candidates < 1 || max_candidates > (long long)INT_MAX) { set_error(name + ": max_candidates must lie in [1, 2^31 - 1]"); return -1; }
 	counts[0] = counts[1] = counts[2] = counts[3] = 0;
@@ -531,15 +482,12 @@ extern "C" int adgs_sparse_tsdf_allocate_view(const adgs_sparse_tsdf_volume* vol
 	const unsigned grid = blocks_for((size_t)pixels, ALLOC_THREADS);
 	ADGS_HIP_CHECK(hipMemsetAsync(t.aux, 0, 2 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
 	ADGS_HIP_CHECK(hipMemsetAsync(t.state, 0, sizeof(AllocState), stream));
-	hipLaunchKernelGGL(sparse_candidates_kernel<false>, dim3(grid), dim3(ALLOC_THREADS), 0, stream, v, depth, opacity, weight, keys, NB, t.wave_base, t.cand, cand_cap,
+	ADGS_LAUNCH(sparse_candidates_kernel<false>, dim3(grid), dim3(ALLOC_THREADS), 0, stream, v, depth, opacity, weight, keys, NB, t.wave_base, t.cand, cand_cap,
 		t.state);
-	ADGS_HIP_CHECK(hipGetLastError());
 	if (exclusive_scan_u32_sum(t.wave_base, t.wave_base, nw, t.scan, t.wave_base, t.aux, stream) != 0) return -1;
-	hipLaunchKernelGGL(sparse_candidate_total_kernel, dim3(1), dim3(1), 0, stream, (const unsigned long long*)t.aux, cand_cap, t.state);
-	ADGS_HIP_CHECK(hipGetLastError());
-	hipLaunchKernelGGL(sparse_candidates_kernel<true>, dim3(grid), dim3(ALLOC_THREADS), 0, stream, v, depth, opacity, weight, keys, NB, t.wave_base, t.cand, cand_cap,
+	ADGS_LAUNCH(sparse_candidate_total_kernel, dim3(1), dim3(1), 0, stream, (const unsigned long long*)t.aux, cand_cap, t.state);
+	ADGS_LAUNCH(sparse_candidates_kernel<true>, dim3(grid), dim3(ALLOC_THREADS), 0, stream, v, depth, opacity, weight, keys, NB, t.wave_base, t.cand, cand_cap,
 		t.state);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return allocate_tail(name, t, cand_cap, vol, keys, slots, keys_out, slots_out, block_coords, counts, stream);
 }
 
@@ -557,8 +505,7 @@ extern "C" int adgs_sparse_tsdf_allocate_blocks(const adgs_sparse_tsdf_volume* v
 	const AllocTemp t = carve_alloc((char*)temp, 0, M);
 	ADGS_HIP_CHECK(hipMemsetAsync(t.aux, 0, 2 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
 	ADGS_HIP_CHECK(hipMemsetAsync(t.state, 0, sizeof(AllocState), stream));
-	hipLaunchKernelGGL(sparse_coord_keys_kernel, dim3(blocks_for((size_t)M, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, coords, (uint32_t)M, t.cand, t.state);
-	ADGS_HIP_CHECK(hipGetLastError());
+	ADGS_LAUNCH(sparse_coord_keys_kernel, dim3(blocks_for((size_t)M, ALLOC_THREADS)), dim3(ALLOC_THREADS), 0, stream, coords, (uint32_t)M, t.cand, t.state);
 	return allocate_tail(name, t, (uint32_t)M, vol, keys, slots, keys_out, slots_out, block_coords, counts, stream);
 }
 
@@ -570,7 +517,7 @@ extern "C" int adgs_sparse_tsdf_integrate(const adgs_sparse_tsdf_volume* vol, co
 	if (check_volume(name, vol, true, L) < 0) return -1;
 	TsdfView v;
 	int steps;
-	if (check_view(name, view, L, v, steps) < 0) return -1;
+	if (check_view_steps(name, view, L, v, steps) < 0) return -1;
 	if ((image != nullptr) != (color != nullptr)) { set_error(name + ": image and color must be given together"); return -1; }
 	if (vol->num_blocks == 0 || view->H == 0 || view->W == 0) return 0;
 	if (!block_coords || !tsdf || !wsum) { set_error(name + ": NULL pointer"); return -1; }
@@ -583,9 +530,8 @@ extern "C" int adgs_sparse_tsdf_integrate(const adgs_sparse_tsdf_volume* vol, co
 	cull.right_r = cull.radius * std::sqrt(v.kx * v.kx + cull.right_b * cull.right_b) * slack;
 	cull.top_r = cull.radius * std::sqrt(v.ky * v.ky + cull.top_b * cull.top_b) * slack;
 	cull.bottom_r = cull.radius * std::sqrt(v.ky * v.ky + cull.bottom_b * cull.bottom_b) * slack;
-	hipLaunchKernelGGL(sparse_integrate_kernel, dim3((unsigned)vol->num_blocks), dim3(INTEGRATE_THREADS), 0, (hipStream_t)stream_, L, v, cull, depth, opacity, image,
+	ADGS_LAUNCH(sparse_integrate_kernel, dim3((unsigned)vol->num_blocks), dim3(INTEGRATE_THREADS), 0, (hipStream_t)stream_, L, v, cull, depth, opacity, image,
 		weight, block_coords, tsdf, wsum, color);
-	ADGS_HIP_CHECK(hipGetLastError());
 	return 0;
 }
 
@@ -611,25 +557,9 @@ extern "C" int adgs_sparse_tsdf_extract_count(const adgs_sparse_tsdf_volume* vol
 	hipStream_t stream = (hipStream_t)stream_;
 	const uint32_t NB = (uint32_t)vol->num_blocks;
 	const ExtractTemp t = carve_extract((char*)temp, NB);
-	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 3 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
-	hipLaunchKernelGGL(sparse_points_kernel<false>, dim3(NB), dim3(EXTRACT_THREADS), 0, stream, L, keys, slots, NB, (uint32_t)vol->capacity, tsdf, wsum,
+	ADGS_LAUNCH(sparse_points_kernel<false>, dim3(NB), dim3(EXTRACT_THREADS), 0, stream, L, keys, slots, NB, (uint32_t)vol->capacity, tsdf, wsum,
 		(const float*)nullptr, min_weight, t.cv, t.cf, t.ce, (uint32_t*)nullptr, 0u, (size_t)0, (float*)nullptr, (float*)nullptr);
-	ADGS_HIP_CHECK(hipGetLastError());
-	uint32_t* rows[3] = { t.cv, t.cf, t.ce };
-	for (int r = 0; r < 3; r++)
-		if (exclusive_scan_u32_sum(rows[r], rows[r], NB, t.scan, rows[r], t.totals + r * SCAN_AUX_SLOTS, stream) != 0) return -1;
-	unsigned long long host[3 * SCAN_AUX_SLOTS];
-	ADGS_HIP_CHECK(hipMemcpyAsync(host, t.totals, sizeof(host), hipMemcpyDeviceToHost, stream));
-	ADGS_HIP_CHECK(hipStreamSynchronize(stream));
-	unsigned long long sum[3] = { 0, 0, 0 };
-	for (int r = 0; r < 3; r++)
-		for (int s = 0; s < SCAN_AUX_SLOTS; s++) sum[r] += host[r * SCAN_AUX_SLOTS + s];
-	if (sum[0] > (unsigned long long)INT_MAX || sum[1] > (unsigned long long)INT_MAX) {
-		set_error(name + ": the mesh has " + std::to_string(sum[0]) + " vertices and " + std::to_string(sum[1]) + " faces; more than INT_MAX of either is refused");
-		return -1;
-	}
-	for (int r = 0; r < 3; r++) counts[r] = (long long)sum[r];
-	return 0;
+	return extract_count_tail(name, t, NB, stream, counts);
 }
 
 extern "C" int adgs_sparse_tsdf_extract_emit(const adgs_sparse_tsdf_volume* vol, const uint64_t* keys, const int* slots, const float* tsdf, const float* wsum,
@@ -641,22 +571,15 @@ extern "C" int adgs_sparse_tsdf_extract_emit(const adgs_sparse_tsdf_volume* vol,
 	if (check_volume(name, vol, true, L) < 0) return -1;
 	if (!(min_weight > 0.f)) { set_error(name + ": min_weight must be > 0"); return -1; }
 	const long long V = counts[0], F = counts[1], E = counts[2], NB = vol->num_blocks;
-	if (V < 0 || F < 0 || E < 0 || V > (long long)INT_MAX || F > (long long)INT_MAX || E > NB || E > V || V > 7 * SBP * NB || F > 12 * SBP * NB) {
-		set_error(name + ": counts are not what adgs_sparse_tsdf_extract_count returned for this volume"); return -1;
-	}
-	if ((V > 0 && !vertices) || (F > 0 && !faces) || (E > 0 && !owners)) { set_error(name + ": NULL vertices, faces or owners"); return -1; }
-	if ((color != nullptr) != (colors != nullptr)) { set_error(name + ": color and colors must be given together"); return -1; }
+	// a point owns at most 7 vertices, a cell has at most 12 faces
+	if (check_emit(name, "adgs_sparse_tsdf_extract_count", counts, 7 * SBP * NB, 12 * SBP * NB, NB, vertices, faces, owners, color, colors) < 0) return -1;
 	if (V == 0 || E == 0) return 0;                              // no vertex, hence no face
 	if (!keys || !slots || !tsdf || !wsum || !temp) { set_error(name + ": NULL pointer"); return -1; }
 	hipStream_t stream = (hipStream_t)stream_;
 	const ExtractTemp t = carve_extract((char*)temp, (size_t)NB);
-	hipLaunchKernelGGL(sparse_points_kernel<true>, dim3((unsigned)NB), dim3(EXTRACT_THREADS), 0, stream, L, keys, slots, (uint32_t)NB, (uint32_t)vol->capacity, tsdf,
+	ADGS_LAUNCH(sparse_points_kernel<true>, dim3((unsigned)NB), dim3(EXTRACT_THREADS), 0, stream, L, keys, slots, (uint32_t)NB, (uint32_t)vol->capacity, tsdf,
 		wsum, color, min_weight, t.cv, t.cf, t.ce, (uint32_t*)owners, (unsigned)E, (size_t)V, vertices, colors);
-	ADGS_HIP_CHECK(hipGetLastError());
-	if (F > 0) {
-		hipLaunchKernelGGL(sparse_faces_kernel, dim3((unsigned)NB), dim3(EXTRACT_THREADS), 0, stream, keys, slots, (uint32_t)NB, (uint32_t)vol->capacity, tsdf, wsum,
-			min_weight, (const uint32_t*)t.cv, (const uint32_t*)t.cf, (const uint32_t*)t.ce, (const uint32_t*)owners, (unsigned)E, (size_t)F, faces);
-		ADGS_HIP_CHECK(hipGetLastError());
-	}
+	if (F > 0) ADGS_LAUNCH(sparse_faces_kernel, dim3((unsigned)NB), dim3(EXTRACT_THREADS), 0, stream, keys, slots, (uint32_t)NB, (uint32_t)vol->capacity, tsdf, wsum,
+		min_weight, (const uint32_t*)t.cv, (const uint32_t*)t.cf, (const uint32_t*)t.ce, (const uint32_t*)owners, (unsigned)E, (size_t)F, faces);
 	return 0;
 }
