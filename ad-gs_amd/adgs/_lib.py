@@ -180,6 +180,12 @@ SIGNATURES = {
     "adgs_mesh_keep_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_mesh_normals_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
     "adgs_mesh_vertex_normals": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    # include/adgs_zbuffer.h
+    "adgs_zbuffer_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_zbuffer_draw": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_zbuffer_interpolate": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_f, c_p, c_p]),
+    "adgs_zbuffer_count_faces": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_zbuffer_keep_faces_count": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     # include/adgs_geometry.h
     "adgs_geometry_grid_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "adgs_geometry_grid_plan": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),

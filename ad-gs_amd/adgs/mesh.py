@@ -159,6 +159,43 @@ def keep_components(comps, keep, vertices, faces, colors=None, normals=None):
 
 
 @torch.no_grad()
+def keep_faces(keep, vertices, faces, colors=None, normals=None):
+    """Keeps the faces with keep [F] True (for example adgs.zbuffer.FaceVisibility.seen()) and the vertices they use -> (vertices, faces,
+    colors or None, normals or None), shaped like keep_components' result: the remaining vertices renumbered densely in their order, the
+    faces in their order with their corner order, the attributes gathered bit for bit; a canonical mesh stays canonical.  A face with an
+    index outside [0, V) is never dereferenced and never kept.  Synchronises once, to learn the sizes."""
+    who = "keep_faces"
+    f = _check_faces(faces, who)
+    dev, F = f.device, int(f.shape[0])
+    v = _check_rows(vertices, "vertices", None, dev, who)
+    V = int(v.shape[0])
+    c = None if colors is None else _check_rows(colors, "colors", V, dev, who)
+    n = None if normals is None else _check_rows(normals, "normals", V, dev, who)
+    if not torch.is_tensor(keep) or keep.dtype != torch.bool or tuple(keep.shape) != (F,):
+        raise ValueError("%s: keep must be a bool [F] = [%d] tensor" % (who, F))
+    if keep.device != dev:
+        raise RuntimeError("%s: keep is on %s, faces on %s" % (who, keep.device, dev))
+    if V >= 2 ** 31:
+        raise ValueError("%s: V must be below 2^31" % who)
+    _need_device(f, who)
+    k8 = keep.detach().contiguous().view(torch.uint8)
+    counts = (ctypes.c_longlong * 3)(0, 0, 0)
+    temp = None
+    if F:
+        temp = torch.empty(int(_lib.lib().adgs_mesh_keep_temp_bytes(V, F)), dtype=torch.uint8, device=dev)
+        _lib.call("adgs_zbuffer_keep_faces_count", dev, V, F, _ptr(f), _ptr(k8), temp.data_ptr(), counts)
+    V2, F2 = int(counts[0]), int(counts[1])
+    vo = torch.empty((V2, 3), dtype=torch.float32, device=dev)
+    fo = torch.empty((F2, 3), dtype=torch.int32, device=dev)
+    co = None if c is None else torch.empty((V2, 3), dtype=torch.float32, device=dev)
+    no = None if n is None else torch.empty((V2, 3), dtype=torch.float32, device=dev)
+    if V2:
+        _lib.call("adgs_mesh_keep_emit", dev, V, F, _ptr(f), v.data_ptr(), _ptr(c), _ptr(n), temp.data_ptr(), counts, vo.data_ptr(), _ptr(fo), _ptr(co),
+                  _ptr(no))
+    return vo, fo, co, no
+
+
+@torch.no_grad()
 def remove_small_components(vertices, faces, colors=None, largest=50, min_faces=50, min_area=None):
     """connected_components, Components.select and keep_components in one call -> (vertices, faces, colors or None): the floaters of a
     fused mesh removed by the 2DGS rule.  Two synchronisations (C, then the sizes)."""

@@ -3,12 +3,14 @@
 //
 //   label    init parent -> link (one launch over the faces) -> flatten (one launch over the vertices) -> root flags -> scan -> component ids
 //   table    one launch over the vertices (root, vertex counts), one over the faces (face counts, areas): one atomic per run of a component
-//   keep     flags from keep[vertex_component] -> two scans -> one emit launch for the vertex attributes, one for the faces
+//   keep     flags from keep[vertex_component] (or, adgs_zbuffer_keep_faces_count, from a per-face mask) -> two scans -> one emit launch
+//            for the vertex attributes, one for the faces
 //   normals  3 F (vertex, corner) pairs -> stable radix sort by vertex -> one thread per vertex finds its row by bisection and sums it in order
 // Every kernel that reads `faces` checks the three indices against V before it uses them (load_face, mesh_shared.h) and skips the face otherwise.
 #include "common.h"
 #include "mesh_shared.h"
 #include "../../include/adgs_mesh.h"
+#include "../../include/adgs_zbuffer.h"
 
 namespace adgs {
 namespace {
@@ -211,6 +213,24 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_keep_flags_kernel(const int
 	}
 }
 
+// The flags of a per-face mask (adgs_zbuffer_keep_faces_count): a face stays when face_keep[f] != 0 and its indices are in range; a vertex
+// when a face that stays uses it -- plain stores of 1 into vflag, which the host zeroed.  The faces that the mask kept and the index check
+// dropped are counted in the UPPER 32 bits of the face row of the scan totals (F' < 2^31 stays below them), one atomic per wave that has any:
+// the KeepTemp layout needs no counter of its own.
+__global__ void __launch_bounds__(MESH_THREADS) mesh_keep_mask_flags_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ face_keep,
+	uint32_t V, uint32_t F, uint32_t* __restrict__ vflag, uint32_t* __restrict__ fflag, unsigned long long* __restrict__ face_totals) {
+	const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
+	uint32_t i[3], k = 0;
+	bool dropped = false;
+	if (f < F && face_keep[f]) {
+		if (load_face(faces, f, V, i)) { k = 1u; vflag[i[0]] = 1u; vflag[i[1]] = 1u; vflag[i[2]] = 1u; }
+		else dropped = true;
+	}
+	if (f < F) fflag[f] = k;
+	const unsigned long long m = __ballot(dropped);
+	if (m && (threadIdx.x & (WAVE - 1)) == 0) atomicAdd(face_totals + (blockIdx.x % SCAN_AUX_SLOTS), (unsigned long long)__popcll(m) << 32);
+}
+
 // map[]: the exclusive scan of the flags; element t was kept when the scan steps behind it
 __device__ __forceinline__ bool kept(const uint32_t* __restrict__ map, uint32_t t, uint32_t n, uint32_t total) {
 	return (t + 1 < n ? map[t + 1] : total) != map[t];
@@ -402,6 +422,29 @@ extern "C" int adgs_mesh_keep_count(int V, int F, int C, const int* faces, const
 	if (read_scan_totals<2, 0>(t.totals, stream, sum, nullptr) != 0) return -1;
 	if (sum[0] > (unsigned long long)V || sum[1] > (unsigned long long)F) { set_error(name + ": a count exceeds INT_MAX"); return -1; }     // cannot happen
 	counts[0] = (long long)sum[0]; counts[1] = (long long)sum[1];
+	return 0;
+}
+
+extern "C" int adgs_zbuffer_keep_faces_count(int V, int F, const int* faces, const unsigned char* face_keep, void* temp, long long* counts, void* stream_) {
+	const std::string name("adgs_zbuffer_keep_faces_count");
+	if (V < 0 || F < 0) { set_error(name + ": negative V or F"); return -1; }
+	if (!counts) { set_error(name + ": NULL counts"); return -1; }
+	if ((F > 0 && (!faces || !face_keep)) || ((V > 0 || F > 0) && !temp)) { set_error(name + ": NULL pointer"); return -1; }
+	counts[0] = counts[1] = counts[2] = 0;
+	if (F == 0) return 0;                                       // no face stays, hence no vertex
+	hipStream_t stream = (hipStream_t)stream_;
+	const KeepTemp t = carve_keep((char*)temp, (size_t)V, (size_t)F);
+	ADGS_HIP_CHECK(hipMemsetAsync(t.totals, 0, 2 * SCAN_AUX_SLOTS * sizeof(unsigned long long), stream));
+	if (V > 0) ADGS_HIP_CHECK(hipMemsetAsync(t.vmap, 0, (size_t)V * sizeof(uint32_t), stream));
+	ADGS_LAUNCH(mesh_keep_mask_flags_kernel, dim3(blocks_of((size_t)F)), dim3(MESH_THREADS), 0, stream, faces, face_keep, (uint32_t)V, (uint32_t)F, t.vmap,
+		t.fmap, t.totals + SCAN_AUX_SLOTS);
+	if (V > 0 && exclusive_scan_u32_sum(t.vmap, t.vmap, (size_t)V, t.scan, t.vmap, t.totals, stream) != 0) return -1;
+	if (exclusive_scan_u32_sum(t.fmap, t.fmap, (size_t)F, t.scan, t.fmap, t.totals + SCAN_AUX_SLOTS, stream) != 0) return -1;
+	unsigned long long sum[2];
+	if (read_scan_totals<2, 0>(t.totals, stream, sum, nullptr) != 0) return -1;
+	const unsigned long long kept = sum[1] & 0xFFFFFFFFull, dropped = sum[1] >> 32;
+	if (sum[0] > (unsigned long long)V || kept + dropped > (unsigned long long)F) { set_error(name + ": a count exceeds INT_MAX"); return -1; }      // cannot happen
+	counts[0] = (long long)sum[0]; counts[1] = (long long)kept; counts[2] = (long long)dropped;
 	return 0;
 }
 

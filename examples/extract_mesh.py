@@ -4,11 +4,13 @@ volume over the static Gaussians' box, extract the surface by marching tetrahedr
 
     for camera:  render(camera)                         one time stamp per render
                  -> vol.integrate(depth, img_opacity, (camera, pose), image=render, weight=static)
-    vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
+    vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.zbuffer.visible_faces -> adgs.mesh.keep_faces]
+        [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
         -> adgs.io.write_mesh_ply
 
     python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json] [--sparse [--margin 2]]
-                                    [--keep-largest K] [--min-faces m] [--simplify CELL [--placement quadric|average]] [--normals]
+                                    [--keep-largest K] [--min-faces m] [--cull-unseen [MIN_VIEWS]] [--simplify CELL [--placement quadric|average]]
+                                    [--normals]
 
 --sparse fuses into a block-sparse volume (adgs.tsdf_sparse) instead of the dense box: no box is chosen, only the 8 x 8 x 8 blocks near the
 rendered surfaces are stored.  It allocates for ALL views first and then integrates them all with allocate=False -- the order that gives
@@ -16,7 +18,9 @@ the dense volume's values (a block allocated by a later view would otherwise mis
 are kept between the two loops.  Everything downstream is the same; --json then also reports the blocks and the bytes held.
 
 --keep-largest / --min-faces (off by default; either one turns the clean-up on, the other then takes its 2DGS default of 50) drop the small
-connected components of the mesh, --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
+connected components of the mesh, --cull-unseen [MIN_VIEWS] (off by default; 1 when given without a number) renders the cleaned mesh again
+from the cameras that were fused (adgs.zbuffer) and keeps the faces that won a pixel in at least MIN_VIEWS of them -- the closed back of
+the truncation band and the far side of half-observed objects go --, --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
 between the clean-up and the normals (adgs.simplify; below one voxel it only welds), --normals writes area-weighted vertex normals into
 the PLY (adgs.mesh).
 
@@ -42,9 +46,9 @@ from multiview_step import neighbour_of  # noqa: E402
 
 
 def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False,
-        simplify=None, placement="quadric", sparse=False, margin=2.0):
+        simplify=None, placement="quadric", sparse=False, margin=2.0, cull_unseen=None):
     import torch
-    from adgs import io, mesh, synthetic, tsdf, tsdf_sparse
+    from adgs import io, mesh, synthetic, tsdf, tsdf_sparse, zbuffer
     from adgs import simplify as simplification
     from adgs.model import SyntheticGaussianModel
     from gaussian_renderer import render
@@ -91,6 +95,13 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
         keep = comps.select(largest=K, min_faces=m)
         vertices, faces, colors, _ = mesh.keep_components(comps, keep, vertices, faces, colors=colors)
         cleanup = {"largest": K, "min_faces": m, "components": len(comps), "kept_components": int(keep.sum())}
+    culled = None
+    if cull_unseen is not None:                                    # after the clean-up, before the simplification
+        before = (int(vertices.shape[0]), int(faces.shape[0]))
+        vis = zbuffer.visible_faces(vertices, faces, list(zip(cams, poses)), (cfg["H"], cfg["W"]))
+        vertices, faces, colors, _ = mesh.keep_faces(vis.seen(min_views=cull_unseen), vertices, faces, colors=colors)
+        culled = {"min_views": cull_unseen, "views": vis.num_views, "vertices_before": before[0], "faces_before": before[1],
+                  "vertices_after": int(vertices.shape[0]), "faces_after": int(faces.shape[0])}
     simplified = None
     if simplify is not None:
         before = (int(vertices.shape[0]), int(faces.shape[0]))
@@ -103,7 +114,7 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
     v2, f2, c2, n2 = io.read_mesh_ply(out, normals=True)
     assert v2.shape == tuple(vertices.shape) and f2.shape == tuple(faces.shape) and c2.shape == tuple(colors.shape)
     assert (n2 is None) == (vnormals is None) and (n2 is None or n2.shape == v2.shape)
-    return {"extracted": extracted, "cleanup": cleanup, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras,
+    return {"extracted": extracted, "cleanup": cleanup, "cull_unseen": culled, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras,
             "dims": box_dims if sparse else list(vol.dims), "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()),
             "sparse": {"blocks": vol.num_blocks, "bytes": int(vol.memory_bytes), "block_bytes": vol.num_blocks * 512 * 20, "margin": margin,
                        "dense_box_bytes": 20 * box_dims[0] * box_dims[1] * box_dims[2], "skipped_samples": vol.skipped_samples} if sparse else None, "vertices": int(vertices.shape[0]),
@@ -120,6 +131,8 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep the components with at least as many faces as the K-th largest")
     ap.add_argument("--min-faces", type=int, default=None, metavar="m", help="and with at least m faces")
+    ap.add_argument("--cull-unseen", type=int, nargs="?", const=1, default=None, metavar="MIN_VIEWS",
+                    help="keep the faces that win a pixel in at least MIN_VIEWS (default 1) of the fused cameras (adgs.zbuffer)")
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a lattice of CELL voxels (adgs.simplify)")
     ap.add_argument("--placement", choices=("quadric", "average"), default="quadric", help="where the vertex of a cluster goes")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
@@ -130,7 +143,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
     res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals, simplify=a.simplify,
-              placement=a.placement, sparse=a.sparse, margin=a.margin)
+              placement=a.placement, sparse=a.sparse, margin=a.margin, cull_unseen=a.cull_unseen)
     if a.json:
         print(json.dumps(res))
     else:
@@ -143,6 +156,10 @@ def main():
             b = res["sparse"]
             print("block-sparse volume: %d blocks, %d bytes held (%d in blocks) against %d for the dense box above; the observed share is of the blocks' points"
                   % (b["blocks"], b["bytes"], b["block_bytes"], b["dense_box_bytes"]))
+        if res["cull_unseen"]:
+            u = res["cull_unseen"]
+            print("culled the faces seen in fewer than %d of %d views: F %d -> %d, V %d -> %d" % (
+                u["min_views"], u["views"], u["faces_before"], u["faces_after"], u["vertices_before"], u["vertices_after"]))
         s = res["simplify"]
         if res["cleanup"] or res["normals"] or s:
             c = res["cleanup"]
