@@ -219,6 +219,8 @@ SIGNATURES = {
     "adgs_test_sort_temp_bytes": (ctypes.c_size_t, [ctypes.c_size_t]),
     "adgs_test_sort_pairs_u64": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
     "adgs_test_sort_pairs_u32": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_i, c_p, c_p]),
+    "adgs_test_exclusive_scan_u32_sum": (c_i, [c_p, c_p, ctypes.c_size_t, c_p, c_p, c_p, c_p]),
+    "adgs_test_sort_pairs_u64_dn": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p, c_i, c_p, c_p]),
     "adgs_test_bilagrid_path": (c_i, [c_i, c_i, c_i, c_i, c_i]),
     "adgs_test_deform_plan": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }

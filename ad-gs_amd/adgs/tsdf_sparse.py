@@ -31,6 +31,10 @@ BLOCK_POINTS = 512                           # ADGS_SPARSE_TSDF_BLOCK_POINTS
 MAX_BLOCKS = 1 << 22                         # ADGS_SPARSE_TSDF_MAX_BLOCKS
 COORD_LIMIT = 1 << 20                        # ADGS_SPARSE_TSDF_COORD_LIMIT
 MAX_STEPS = 64                               # ADGS_SPARSE_TSDF_MAX_STEPS
+# the scratch for the candidate keys a view's allocation starts with: at least MIN_CANDIDATES keys and CANDIDATES_PER_WAVE for every 64
+# pixels (a wave of the candidate kernel); a view with more is told so and retried with room (SparseTSDFVolume._allocating_call)
+MIN_CANDIDATES = 4096
+CANDIDATES_PER_WAVE = 16
 
 
 class SparseTsdfVolumeDesc(ctypes.Structure):
@@ -241,7 +245,7 @@ class SparseTSDFVolume:
         if not d.numel():
             return 0
         pixels = d.numel()
-        candidates = max(self._max_candidates, 4096, 16 * -(-pixels // 64))
+        candidates = max(self._max_candidates, MIN_CANDIDATES, CANDIDATES_PER_WAVE * -(-pixels // 64))
         return self._allocating_call(who, "adgs_sparse_tsdf_allocate_view", pixels, candidates,
                                      (ctypes.byref(view), self.margin, d.data_ptr(), o.data_ptr(), _ptr(w)), pass_candidates=True)
 

@@ -1600,3 +1600,9 @@ extern "C" int adgs_test_sort_pairs_u64(uint64_t* ki, uint64_t* ko, uint32_t* vi
 extern "C" int adgs_test_sort_pairs_u32(uint32_t* ki, uint32_t* ko, uint32_t* vi, uint32_t* vo, size_t n, int end_bit, char* temp, void* stream) {
 	return radix_sort_pairs_u32(ki, ko, vi, vo, n, end_bit, temp, (hipStream_t)stream);
 }
+extern "C" int adgs_test_exclusive_scan_u32_sum(const uint32_t* in, uint32_t* out, size_t n, char* temp, const uint32_t* aux_in, unsigned long long* aux_total, void* stream) {
+	return exclusive_scan_u32_sum(in, out, n, temp, aux_in, aux_total, (hipStream_t)stream);
+}
+extern "C" int adgs_test_sort_pairs_u64_dn(uint64_t* ki, uint64_t* ko, uint32_t* vi, uint32_t* vo, size_t n_cap, const uint32_t* d_n, int end_bit, char* temp, void* stream) {
+	return radix_sort_pairs_u64_dn(ki, ko, vi, vo, n_cap, d_n, end_bit, temp, (hipStream_t)stream);
+}

@@ -18,6 +18,12 @@ size_t adgs_test_sort_temp_bytes(size_t n);
 /* stable LSD radix sort on key bits [0,end_bit); *_in are clobbered */
 int adgs_test_sort_pairs_u64(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n, int end_bit, char* temp, void* stream);
 int adgs_test_sort_pairs_u32(uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n, int end_bit, char* temp, void* stream);
+/* the scan above plus, when aux_in is given, sum(aux_in[0..n)) ADDED into the 32 counters aux_total[] (the caller adds them up);
+ * in == out == aux_in allowed; aux_in == NULL leaves the counters alone */
+int adgs_test_exclusive_scan_u32_sum(const uint32_t* in, uint32_t* out, size_t n, char* temp, const uint32_t* aux_in, unsigned long long* aux_total /* 32 slots */, void* stream);
+/* the u64 sort with the count read on the device: sorts the first min(*d_n, n_cap) pairs; n_cap sizes the launch, the temporaries
+ * (adgs_test_sort_temp_bytes(n_cap)) and all four arrays; out[min(*d_n, n_cap) .. n_cap) holds no result */
+int adgs_test_sort_pairs_u64_dn(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n_cap, const uint32_t* d_n, int end_bit, char* temp, void* stream);
 /* Number of (tile, Gaussian) entries the default (v2) forward published for the backward replay of a frame: the sum of the
  * per-tile counts in the forward's image-state buffer.  Synchronises the stream; statistics only (bench.py). */
 long long adgs_test_v2_published_entries(const char* img_buffer, int width, int height, void* stream);

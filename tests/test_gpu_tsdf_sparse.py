@@ -296,3 +296,96 @@ def test_interleaved_allocation_is_another_volume():
     assert torch.equal(torch.sort(first.keys).values, interleaved.keys)
     rows = first.slots[torch.searchsorted(first.keys, interleaved.keys[torch.argsort(interleaved.slots)])].long()      # first's row of each of interleaved's
     assert bool((interleaved.wsum <= first.wsum[rows]).all()) and bool((interleaved.wsum < first.wsum[rows]).any())
+
+
+def test_truncated_allocation_through_the_abi():
+    """adgs_sparse_tsdf_allocate_view with less scratch than the view has candidates: the emit pass drops candidates, the sort is given the cap
+    and a device-side count, and the call returns 1 with counts[1] = what it needs.  It must leave the table it read, block_coords[:NB] and the pool
+    alone (its outputs hold no result then); the call with exactly counts[1] candidates gives what a call with ample room gives."""
+    import ctypes
+    from adgs import _lib, tsdf, tsdf_sparse
+    name = "base"
+    views = cases.views(name)
+    v = new_volume(name)
+    args, kw = view_args(views[0], name, image=False)
+    assert v.allocate(*args, **kw) > 0                          # a table that is not empty: the candidates are filtered against it
+    NB, room = v.num_blocks, v.num_blocks + 4096
+    (depth, opacity, camera), kw = view_args(views[1], name, image=False)
+    H, W, tan, pose, mo, nr, md, d, o, _, w = tsdf._view_arguments("test", v.device, False, depth, opacity, camera, None, kw["weight"], kw["min_opacity"],
+                                                                   kw["max_depth"], kw["near"])
+    view = tsdf.make_view_desc(H, W, kw["inv_depth"], tan, mo, nr, md, v.trunc, v.max_weight, pose)
+    keys, slots = v.keys.clone(), v.slots.clone()
+    pool = [t.clone() for t in (v.tsdf, v.wsum, v.color)]
+
+    def call(max_candidates):
+        keys_out = torch.full((room,), -1, dtype=torch.int64, device="cuda")
+        slots_out = torch.full((room,), -1, dtype=torch.int32, device="cuda")
+        coords = torch.full((room, 3), -77, dtype=torch.int32, device="cuda")
+        coords[:NB] = v.block_coords
+        temp = torch.empty(int(_lib.lib().adgs_sparse_tsdf_allocate_temp_bytes(H * W, max_candidates)), dtype=torch.uint8, device="cuda")
+        counts = (ctypes.c_longlong * 4)(-1, -1, -1, -1)
+        desc = tsdf_sparse.make_sparse_volume_desc(NB, v.capacity, room, v.voxel_size, v.origin)
+        code = _lib.call("adgs_sparse_tsdf_allocate_view", v.device, ctypes.byref(desc), ctypes.byref(view), v.margin, d.data_ptr(), o.data_ptr(), w.data_ptr(),
+                         keys.data_ptr(), slots.data_ptr(), keys_out.data_ptr(), slots_out.data_ptr(), coords.data_ptr(), max_candidates, temp.data_ptr(), counts)
+        # whatever the outcome, the call only reads these
+        assert torch.equal(keys, v.keys) and torch.equal(slots, v.slots) and torch.equal(coords[:NB], v.block_coords)
+        for a, b in zip(pool, (v.tsdf, v.wsum, v.color)):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+        return code, [int(x) for x in counts], keys_out, slots_out, coords
+
+    code, counts, _, _, _ = call(1)
+    print("max_candidates = 1 with %d blocks in the table: code %d, counts %s" % (NB, code, counts))
+    assert code == 1 and counts[3] == 1 and counts[1] > 1
+    found = counts[1]
+    code, exact, keys_exact, slots_exact, coords_exact = call(found)
+    assert code == 0 and exact[1] == found and exact[3] == 0
+    code, ample, keys_ample, slots_ample, coords_ample = call(4 * found + 4096)
+    assert code == 0 and ample[1] == found and ample[3] == 0
+    new = ample[0]
+    assert new > 0 and exact[0] == new and exact[2] == ample[2]
+    assert torch.equal(keys_exact[:NB + new], keys_ample[:NB + new]) and torch.equal(slots_exact[:NB + new], slots_ample[:NB + new])
+    assert torch.equal(coords_exact[NB:NB + new], coords_ample[NB:NB + new])
+    # and that is what the volume makes of the view
+    args, kw = view_args(views[1], name, image=False)
+    assert v.allocate(*args, **kw) == new
+    assert torch.equal(v.keys, keys_ample[:NB + new]) and torch.equal(v.slots, slots_ample[:NB + new]) and torch.equal(v.block_coords, coords_ample[:NB + new])
+
+
+@pytest.mark.parametrize("per_wave", [1, 0])
+def test_allocation_retries_with_the_room_the_call_asks_for(monkeypatch, per_wave):
+    """SparseTSDFVolume with a scratch floor of 27 candidates (one per wave of the 36 x 48 views; per_wave = 1) or of a single one (per_wave = 0)
+    instead of 4096: the first call of a view with more candidates than that is told there is no room, and the retry with found + found // 4
+    gives the volume an unpatched one builds.  The last view has 23 candidates once the first three are in the table, so only the floor of 1 sends
+    every view through the retry."""
+    from adgs import _lib, tsdf_sparse
+    name = "base"
+    views = [view_args(view, name, image=False) for view in cases.views(name)]
+    plain, tight = new_volume(name), new_volume(name)
+    for args, kw in views:
+        plain.allocate(*args, **kw)
+    monkeypatch.setattr(tsdf_sparse, "MIN_CANDIDATES", 1)
+    monkeypatch.setattr(tsdf_sparse, "CANDIDATES_PER_WAVE", per_wave)
+    log, real = [], _lib.call
+
+    def recording(symbol, *a):
+        code = real(symbol, *a)
+        if symbol == "adgs_sparse_tsdf_allocate_view":
+            log.append((code, int(a[-3]), int(a[-1][1])))       # return code, max_candidates, counts[1]
+        return code
+    monkeypatch.setattr(_lib, "call", recording)
+    floor = max(1, per_wave * -(-cases.H * cases.W // 64))
+    retried = 0
+    for n, (args, kw) in enumerate(views):
+        del log[:]
+        tight._max_candidates = 0                               # forget the scratch the last view needed: every view starts from the floor
+        new = tight.allocate(*args, **kw)
+        print("view %d: %d new blocks; (code, max_candidates, candidates) per call: %s" % (n, new, log))
+        found = log[0][2]
+        if found > floor:
+            assert log == [(1, floor, found), (0, found + found // 4, found)] and tight._max_candidates == found + found // 4
+            retried += 1
+        else:
+            assert log == [(0, floor, found)] and tight._max_candidates == 0
+    assert retried == len(views) if per_wave == 0 else retried >= 1
+    assert tight.num_blocks == plain.num_blocks > 100 and tight.skipped_samples == plain.skipped_samples
+    assert torch.equal(tight.keys, plain.keys) and torch.equal(tight.slots, plain.slots) and torch.equal(tight.block_coords, plain.block_coords)
