@@ -202,6 +202,12 @@ SIGNATURES = {
     "adgs_simplify_cluster_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "adgs_simplify_place_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
     "adgs_simplify_place": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_p]),
+    # include/adgs_smooth.h
+    "adgs_smooth_adjacency_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_smooth_adjacency_count": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_smooth_adjacency_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "adgs_smooth_steps_temp_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "adgs_smooth_steps": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_i, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
     # include/adgs_testing.h
     "adgs_test_v2_published_entries": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),
     "adgs_test_v2_scanned_candidates": (ctypes.c_longlong, [c_p, c_i, c_i, c_p]),

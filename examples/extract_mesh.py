@@ -5,12 +5,13 @@ volume over the static Gaussians' box, extract the surface by marching tetrahedr
     for camera:  render(camera)                         one time stamp per render
                  -> vol.integrate(depth, img_opacity, (camera, pose), image=render, weight=static)
     vol.extract_mesh() [-> adgs.mesh.remove_small_components] [-> adgs.zbuffer.visible_faces -> adgs.mesh.keep_faces]
-        [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
+        [-> adgs.smooth.smooth_mesh] [-> adgs.simplify.simplify_mesh] [-> adgs.mesh.vertex_normals]
         -> adgs.io.write_mesh_ply
 
     python examples/extract_mesh.py [--config T3] [--cameras 6] [--resolution 160] [--out mesh.ply] [--json] [--sparse [--margin 2]]
-                                    [--keep-largest K] [--min-faces m] [--cull-unseen [MIN_VIEWS]] [--simplify CELL [--placement quadric|average]]
-                                    [--normals]
+                                    [--keep-largest K] [--min-faces m] [--cull-unseen [MIN_VIEWS]]
+                                    [--smooth ITER [--smooth-method taubin|laplacian] [--free-boundary]]
+                                    [--simplify CELL [--placement quadric|average]] [--normals]
 
 --sparse fuses into a block-sparse volume (adgs.tsdf_sparse) instead of the dense box: no box is chosen, only the 8 x 8 x 8 blocks near the
 rendered surfaces are stored.  It allocates for ALL views first and then integrates them all with allocate=False -- the order that gives
@@ -20,7 +21,9 @@ are kept between the two loops.  Everything downstream is the same; --json then 
 --keep-largest / --min-faces (off by default; either one turns the clean-up on, the other then takes its 2DGS default of 50) drop the small
 connected components of the mesh, --cull-unseen [MIN_VIEWS] (off by default; 1 when given without a number) renders the cleaned mesh again
 from the cameras that were fused (adgs.zbuffer) and keeps the faces that won a pixel in at least MIN_VIEWS of them -- the closed back of
-the truncation band and the far side of half-observed objects go --, --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
+the truncation band and the far side of half-observed objects go --, --smooth ITER (off by default) smooths the vertices after the
+clean-up and the culling and before the simplification and the normals (adgs.smooth: Taubin by default, which does not shrink the mesh;
+boundary vertices stay where they are unless --free-boundary), --simplify CELL (in voxels of the volume; off by default) clusters the vertices on a lattice of that cell
 between the clean-up and the normals (adgs.simplify; below one voxel it only welds), --normals writes area-weighted vertex normals into
 the PLY (adgs.mesh).
 
@@ -46,10 +49,11 @@ from multiview_step import neighbour_of  # noqa: E402
 
 
 def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, keep_largest=None, min_faces=None, normals=False,
-        simplify=None, placement="quadric", sparse=False, margin=2.0, cull_unseen=None):
+        simplify=None, placement="quadric", sparse=False, margin=2.0, cull_unseen=None, smooth=None, smooth_method="taubin", free_boundary=False):
     import torch
     from adgs import io, mesh, synthetic, tsdf, tsdf_sparse, zbuffer
     from adgs import simplify as simplification
+    from adgs import smooth as smoothing
     from adgs.model import SyntheticGaussianModel
     from gaussian_renderer import render
     device = device or torch.device("cuda", 0)
@@ -102,6 +106,11 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
         vertices, faces, colors, _ = mesh.keep_faces(vis.seen(min_views=cull_unseen), vertices, faces, colors=colors)
         culled = {"min_views": cull_unseen, "views": vis.num_views, "vertices_before": before[0], "faces_before": before[1],
                   "vertices_after": int(vertices.shape[0]), "faces_after": int(faces.shape[0])}
+    smoothed = None
+    if smooth is not None:                                         # before the simplification and the normals: both read the faces' planes
+        adj = smoothing.mesh_adjacency(faces, int(vertices.shape[0]))
+        vertices = smoothing.smooth_mesh(vertices, faces, smooth, method=smooth_method, boundary="free" if free_boundary else "fixed", adjacency=adj)
+        smoothed = dict(adj.counts, iterations=smooth, method=smooth_method, boundary="free" if free_boundary else "fixed")
     simplified = None
     if simplify is not None:
         before = (int(vertices.shape[0]), int(faces.shape[0]))
@@ -114,7 +123,7 @@ def run(config="T3", cameras=6, resolution=160, out="mesh.ply", device=None, kee
     v2, f2, c2, n2 = io.read_mesh_ply(out, normals=True)
     assert v2.shape == tuple(vertices.shape) and f2.shape == tuple(faces.shape) and c2.shape == tuple(colors.shape)
     assert (n2 is None) == (vnormals is None) and (n2 is None or n2.shape == v2.shape)
-    return {"extracted": extracted, "cleanup": cleanup, "cull_unseen": culled, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras,
+    return {"extracted": extracted, "cleanup": cleanup, "cull_unseen": culled, "smooth": smoothed, "simplify": simplified, "normals": bool(normals), "cleanup_and_normals_ms": 1e3 * (t3 - t2),"config": config, "image": [cfg["H"], cfg["W"]], "gaussians": int(model.get_pts_num), "cameras": cameras,
             "dims": box_dims if sparse else list(vol.dims), "voxel_size": voxel, "observed_share": float((vol.wsum > 0).float().mean()),
             "sparse": {"blocks": vol.num_blocks, "bytes": int(vol.memory_bytes), "block_bytes": vol.num_blocks * 512 * 20, "margin": margin,
                        "dense_box_bytes": 20 * box_dims[0] * box_dims[1] * box_dims[2], "skipped_samples": vol.skipped_samples} if sparse else None, "vertices": int(vertices.shape[0]),
@@ -133,6 +142,9 @@ def main():
     ap.add_argument("--min-faces", type=int, default=None, metavar="m", help="and with at least m faces")
     ap.add_argument("--cull-unseen", type=int, nargs="?", const=1, default=None, metavar="MIN_VIEWS",
                     help="keep the faces that win a pixel in at least MIN_VIEWS (default 1) of the fused cameras (adgs.zbuffer)")
+    ap.add_argument("--smooth", type=int, default=None, metavar="ITER", help="smooth the vertices with ITER iterations (adgs.smooth)")
+    ap.add_argument("--smooth-method", choices=("taubin", "laplacian"), default="taubin", help="taubin does not shrink the mesh, laplacian does")
+    ap.add_argument("--free-boundary", action="store_true", help="with --smooth: let the boundary vertices move too")
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a lattice of CELL voxels (adgs.simplify)")
     ap.add_argument("--placement", choices=("quadric", "average"), default="quadric", help="where the vertex of a cluster goes")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
@@ -143,7 +155,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: there is no CPU fallback")
     res = run(a.config, a.cameras, a.resolution, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, normals=a.normals, simplify=a.simplify,
-              placement=a.placement, sparse=a.sparse, margin=a.margin, cull_unseen=a.cull_unseen)
+              placement=a.placement, sparse=a.sparse, margin=a.margin, cull_unseen=a.cull_unseen, smooth=a.smooth, smooth_method=a.smooth_method,
+              free_boundary=a.free_boundary)
     if a.json:
         print(json.dumps(res))
     else:
@@ -160,6 +173,11 @@ def main():
             u = res["cull_unseen"]
             print("culled the faces seen in fewer than %d of %d views: F %d -> %d, V %d -> %d" % (
                 u["min_views"], u["views"], u["faces_before"], u["faces_after"], u["vertices_before"], u["vertices_after"]))
+        if res["smooth"]:
+            m = res["smooth"]
+            print("smoothed with %d %s iterations, boundary %s: %d edges, %d boundary, %d non-manifold; %d degenerate faces, %d isolated vertices" % (
+                m["iterations"], m["method"], m["boundary"], m["edges"], m["boundary_edges"], m["nonmanifold_edges"], m["degenerate_faces"],
+                m["isolated_vertices"]))
         s = res["simplify"]
         if res["cleanup"] or res["normals"] or s:
             c = res["cleanup"]
